@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- VMG-REDS-few_levels training step (forward + loss + backward + AdamW) on synthetic REDS-shaped clips.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 Workload = BASELINE.json configs[1]: per-GPU batch 4 x 7 x 3 x 64 x 64, 4x SR, bf16 activations (fp32 accumulate,
 fp32 master weights), random-init weights, synthetic data resident in HBM before the timed region.  One "step" is one
-pass of the hot path over one batch.  Prints ONE JSON line on rank 0 with the whole-job LR-frames/s, the roofline
-object of the dominant kernel (live HIP-event timing of the bf16 conv3x3 144->144 weight-streaming kernel) and the CPU
-baseline (the oracle, i.e. this repo's CPU restatement, on one step of the same batch).  --workload train_full / infer /
-train_vimeo run the per-GPU shards of BASELINE configs[2] / [3] / [4] (the last with bf16 weights).
+pass of the hot path over one batch.  A plain run sets up, runs W untimed and K timed steps and prints ONE JSON line on
+rank 0 with the whole-job LR-frames/s and ms_per_step.  --full adds what the headline does not need: the roofline object
+of the dominant kernel (live HIP-event timing of the bf16 conv3x3 144->144 weight-streaming kernel, sampled inside the
+timed steps), the CPU baseline (the oracle, i.e. this repo's CPU restatement, on one step of the same batch) with the
+parity of the benchmarked batch, and the short runs of the other configurations (`extra_workloads`).  --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy.  --workload train_full / infer / train_vimeo run the per-GPU
+shards of BASELINE configs[2] / [3] / [4] (the last with bf16 weights).
 """
 import argparse
 import ctypes
@@ -189,8 +192,27 @@ def recorded_roofline(workload):
             "measured": "recorded: rocprofv3 --kernel-trace average of the eager run of this command, " + rec["source"] + " (a replayed graph cannot be sampled by events)"}
 
 
+DUMP_SAMPLE = 1 << 22  # --dump-outputs: elements per array at most (16 MB in float32; at most two arrays per workload)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: name -> tensor of the last timed step, written as outdir/<name>.npy (float64 stays float64, everything else becomes float32).
+    An array of more than DUMP_SAMPLE elements is written as a fixed sample instead: the elements at DUMP_SAMPLE flat positions drawn from a
+    generator seeded with 0 (sorted), i.e. the same positions in every run of the same workload."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()  # (the inference step hands back a host numpy array)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy())
+
+
 def run_extra(workload, device, steps, warmup, graph):
-    """A short timed run of another BASELINE configuration in the same process, AFTER the headline timing (so the driver's default run times
+    """A short timed run of another BASELINE configuration in the same process, AFTER the headline timing (so a --full run times
     them too): train_full = the per-GPU shard of configs[2] replayed from a captured hipGraph, infer = configs[3] (one 100-frame sequence per
     step).  Same discipline as the headline: W untimed warm-up steps, K timed steps between synchronisations, inputs resident in HBM."""
     from vmg_amd import infer
@@ -238,23 +260,34 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="train", help="train = BASELINE configs[1] (the metric's own "
                     "configuration, the default); train_full / infer = the per-GPU shard of configs[2] / configs[3]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the live HIP-event roofline of the dominant "
+                    "kernel (sampled inside the timed steps), the parity pre-pass and the CPU oracle baseline, and (default workload, one GPU) the "
+                    "short runs of the other BASELINE configurations as `extra_workloads`; --no-prof / --no-cpu-baseline / --no-extras leave parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): "
+                    "train workloads loss.npy and params.npy (a fixed seeded sample of the updated parameters), infer frames.npy (a fixed "
+                    "seeded sample of the uint8 frames); same arguments, same inputs (e.g. DIR = bench_outputs, git-ignored)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no parity pre-pass and no cpu_baseline")
     ap.add_argument("--fp8", action="store_true", help="VMG(fp8_chains=True): conv1 / conv2 of the recurrent chains' residual blocks in fp8 (e4m3, block-scaled "
                     "MFMA; SURVEY 8f-4 / BASELINE configs[4]) in the forward pass; the roofline object then prices the fp8 kernel against the 5 PFLOP/s fp8 peak")
-    ap.add_argument("--no-prof", action="store_true")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: no live HIP-event roofline")
     ap.add_argument("--wgrad3-variant", type=int, default=-1, help="vmg_conv_wgrad3_variant (0: round 2's kernel, 1: conv_wgrad3b_kernel; -1 keeps the default): A/B on one box")
     ap.add_argument("--grouped-dense", type=int, default=-1, help="functional.GROUPED_DENSE (0: grouped convolutions as G launches, 1: one launch on the dense block-diagonal pack; -1 keeps the default): A/B on one box")
     ap.add_argument("--win3d-variant", type=int, default=-1, help="vmg_win3d_variant (0: VALU window-attention kernel, 1: MFMA; -1 keeps the default): A/B on one box")
     ap.add_argument("--spynet-edge-fp32", type=int, default=-1, help="override SPyNet.edge_fp32 (0 / 1; -1 keeps the model's default): A/B of its cost")
-    ap.add_argument("--no-extras", action="store_true", help="skip the short runs of the other BASELINE configurations that the default "
-                    "(--workload train, one GPU) run appends as `extra_workloads`")
-    ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (measured +2 %; the live "
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the short runs of the other BASELINE configurations that a "
+                    "--workload train, one-GPU run appends as `extra_workloads`")
+    ap.add_argument("--graph", action="store_true", help="replay the step from a captured hipGraph (measured +2 %%; the live "
                     "HIP-event roofline needs eager launches, so eager is the default)")
     ap.add_argument("--recompute", action="store_true", help="VMG(recompute_chains=True): the recurrent residual chains keep only their inputs and "
                     "are re-run in the backward (SURVEY 8f-4); prints the peak device memory next to the throughput")
     ap.add_argument("--replay", action="store_true", help="with --graph: re-issue the captured launches with plain hipLaunchKernel calls "
-                    "(vmg_replay_run) instead of hipGraphLaunch -- a measurement of the launch path only (+1 %), see TrainStep.capture")
+                    "(vmg_replay_run) instead of hipGraphLaunch -- a measurement of the launch path only (+1 %%), see TrainStep.capture")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    prof = args.full and not args.no_prof
+    cpu_base = args.full and not args.no_cpu_baseline
+    run_extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start N fresh ranks (one per GPU, RCCL) as CHILD processes and pass rank 0's
@@ -317,7 +350,7 @@ def main():
         Hh, Ww = S if isinstance(S, tuple) else (S, S)
         lrs = synthetic_clip(B, Tn, Hh, Ww, seed=1234 + rank, device=device)
         hrs = synthetic_target(lrs, seed=4321 + rank)
-        if args.workload == "train" and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.workload == "train" and rank == 0 and world == 1 and cpu_base:
             # parity of the benchmarked batch itself (outside the timed region): the network's output for the bench's own clip and INITIAL weights,
             # call #1, DropPath off (eval mode: the oracle draws no masks) -- at this batch the recurrent chains take the
             # weight-streaming route (M = 32 768 pixels), the one the roofline object prices.  The oracle computes the same call on the host
@@ -371,12 +404,12 @@ def main():
     if rank == 0:
         print("[bench] warmup done", file=sys.stderr, flush=True)
     null_us = 0.0
-    if not args.no_prof:
+    if prof:
         null_us = float(lib.vmg_prof_null_interval_us(50, hip.stream_ptr()))  # event-pair interval of an empty kernel
         hip.check(lib.vmg_prof_select_pixels(hip.ctx(), k1_pixels), "vmg_prof_select_pixels")
         # every 64th launch of the class is bracketed by an event pair (class 1: the bf16 conv3x3 C -> C; 3: the fp8 one).  An event pair is
         # not free on this runtime -- ~8 us of stream time per sampled launch: at every 16th launch (54 samples per train step) the sampling
-        # itself cost 0.43 ms per step (A/B against --no-prof); 13 samples per step still give >= 50 per default run
+        # itself cost 0.43 ms per step (A/B against --no-prof); 13 samples per step still give >= 50 per --full run
         hip.check(lib.vmg_prof_begin(hip.ctx(), 3 if args.fp8 else 1, 64, 4096), "vmg_prof_begin")
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -387,9 +420,14 @@ def main():
     if distributed:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    train = args.workload != "infer"
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step holds after the last one: the loss it returned and the parameters it updated (train), the frames (infer)
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])}
+                     if train else {"frames": loss})
 
     roofline = None
-    if not args.no_prof:
+    if prof:
         seen, n, ms = ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_double(0.0)
         hip.check(lib.vmg_prof_end(hip.ctx(), ctypes.byref(seen), ctypes.byref(n), ctypes.byref(ms)), "vmg_prof_end")
         if n.value > 0:
@@ -424,7 +462,6 @@ def main():
         print("[bench] timed region done: %.3f s for %d steps" % (dt, args.steps), file=sys.stderr, flush=True)
     frames = world * B * Tn * args.steps
     value = frames / dt
-    train = args.workload != "infer"
     line = {
         "metric": ("LR-frames/s (train: forward+loss+backward+AdamW), VMG-REDS%s 4x SR" % ("-few_levels" if wl["cfg"] == "few" else "")) if train
         else "LR-frames/s (sliding-window inference incl. tile blending and uint8 conversion), VMG-REDS-few_levels 4x SR",
@@ -448,7 +485,7 @@ def main():
     line["config"]["peak_device_memory_GB"] = round(torch.cuda.max_memory_allocated(device) / 1e9, 2)
     if args.workload == "train":
         line["config"]["model_tflops"] = round(3 * FWD_GFLOP_PER_FRAME * value / 1e3, 2)
-    if args.workload == "train" and world == 1 and not args.no_extras and not args.graph:
+    if args.workload == "train" and world == 1 and run_extras and not args.graph:
         # the other single-GPU configurations, timed by the same run (only the default workload was driver-timed).
         # After the headline's timed region; an extra that fails is reported as such and never takes the headline down with it.
         extras = []
@@ -465,7 +502,7 @@ def main():
         line["extra_workloads"] = extras
     if rank == 0:
         line["parity"] = None
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_base and world == 1:
             if parity_gpu is not None:
                 out_gpu, loss_gpu, sd0, x0, y0 = parity_gpu
                 line["cpu_baseline"], kept = cpu_baseline(args.workload, same=(sd0, x0, y0))

@@ -7,7 +7,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof -o t -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extras > $O/r04_bench_under_prof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof -o t -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extras > $O/r04_bench_under_prof.json 2>/dev/null
 T=$(ls $O/r04_prof/*kernel_trace.csv | head -1)
 cp $(ls $O/r04_prof/*kernel_stats.csv | head -1) $O/r04_bench_kernel_stats.csv
 python3 tools/step_kernels.py $T 60 > $O/r04_step_kernels.txt
@@ -34,5 +34,5 @@ for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE";
   rm -rf $O/pmc_k1_$tag
 done
 echo "[prof] dominant kernel counters done"
-python3 bench.py --steps 20 --warmup 5 > $O/r04_bench_train.json 2> $O/r04_bench_train.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/r04_bench_train.json 2> $O/r04_bench_train.err
 head -c 400 $O/r04_bench_train.json

@@ -6,7 +6,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof -o t -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/r04_prof -o t -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extras > /dev/null 2>&1
 T=$(ls $O/r04_prof/*kernel_trace.csv | head -1)
 cp $(ls $O/r04_prof/*kernel_stats.csv | head -1) $O/r04_c_bench_kernel_stats.csv
 python3 tools/step_kernels.py $T 60 > $O/r04_c_step_kernels.txt
@@ -26,13 +26,13 @@ for pmc in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VALU SQ_INSTS_LD
   rm -rf $O/pmc_w3d_$tag
 done
 echo "[prof] win3d counters done"
-python3 bench.py --steps 20 --warmup 5 > $O/r04_c_bench_train.json 2> $O/r04_c_bench_train.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/r04_c_bench_train.json 2> $O/r04_c_bench_train.err
 echo "[prof] default line done"
-python3 bench.py --workload train_swin --steps 8 --warmup 3 > $O/r04_c_bench_swin.json 2>/dev/null
-python3 bench.py --workload train_vimeo --steps 3 --warmup 2 > $O/r04_c_bench_vimeo_bf16.json 2>/dev/null
+python3 bench.py --full --workload train_swin --steps 8 --warmup 3 > $O/r04_c_bench_swin.json 2>/dev/null
+python3 bench.py --full --workload train_vimeo --steps 3 --warmup 2 > $O/r04_c_bench_vimeo_bf16.json 2>/dev/null
 echo "[prof] vimeo bf16 done"
-python3 bench.py --workload train_vimeo --steps 3 --warmup 2 --fp8 > $O/r04_c_bench_vimeo_fp8.json 2>/dev/null
+python3 bench.py --full --workload train_vimeo --steps 3 --warmup 2 --fp8 > $O/r04_c_bench_vimeo_fp8.json 2>/dev/null
 echo "[prof] vimeo fp8 done"
-python3 bench.py --workload infer --steps 1 --warmup 1 --graph > $O/r04_c_bench_infer_graph.json 2>/dev/null
-python3 bench.py --workload train_full --steps 8 --warmup 3 --graph > $O/r04_c_bench_full_graph.json 2>/dev/null
+python3 bench.py --full --workload infer --steps 1 --warmup 1 --graph > $O/r04_c_bench_infer_graph.json 2>/dev/null
+python3 bench.py --full --workload train_full --steps 8 --warmup 3 --graph > $O/r04_c_bench_full_graph.json 2>/dev/null
 for f in train swin vimeo_bf16 vimeo_fp8 infer_graph full_graph; do head -c 260 $O/r04_c_bench_$f.json | tail -c 140; echo; done

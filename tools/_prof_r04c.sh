@@ -9,5 +9,5 @@ python3 tools/step_kernels.py $T 80 > $O/r04_e_full_step_kernels.txt
 python3 tools/kernel_shapes.py $T conv_ > $O/r04_e_full_conv_launches.txt
 python3 tools/prof_summary.py $T 80 $O/r04_e_full_laststep_summary.txt
 rm -rf $O/r04_prof
-python3 bench.py --workload train_full --steps 8 --warmup 3 --graph > $O/r04_e_bench_full_graph.json 2>/dev/null
+python3 bench.py --full --workload train_full --steps 8 --warmup 3 --graph > $O/r04_e_bench_full_graph.json 2>/dev/null
 head -c 300 $O/r04_e_bench_full_graph.json
