@@ -35,6 +35,13 @@ extern "C" {
 #define VMG_ACT_LRELU 2 /* slope argument */
 #define VMG_ACT_GELU 3  /* erf form, torch nn.GELU() default */
 
+/* convolution kernel routes (vmg_conv_desc::deep; described there) */
+#define VMG_CONV_GENERAL 0     /* general pixel-split kernel */
+#define VMG_CONV_KSPLIT 2      /* K split over the four waves */
+#define VMG_CONV_WS 3          /* weight-streaming 3x3 */
+#define VMG_CONV_LINEAR_WRES 4 /* wave-autonomous 1x1 */
+#define VMG_CONV_WSTAT 6       /* weights-stationary 3x3 */
+
 const char* vmg_last_error(void);
 int vmg_version(void);
 
@@ -70,7 +77,7 @@ int64_t vmg_conv_pack_bytes(int dtype, int ks, int on, int nsrc, const int* src_
 int vmg_conv_pack(int dtype, const float* w, int O, int I, int ks, int o0, int on, int nsrc, const int* src_off,
                   const int* src_ch, int transpose_flip, int cout_tiles, void* packed, void* stream);
 
-/* Packing for the weight-streaming 3x3 kernel (vmg_conv_fwd with deep = 3; bf16 only): same slicing arguments as
+/* Packing for the weight-streaming 3x3 kernel (vmg_conv_fwd with deep = VMG_CONV_WS; bf16 only): same slicing arguments as
  * vmg_conv_pack.  Image: [cout block][stage][3 k-steps][4 lane groups][co in block][8] bf16, a k-step = one tap of a 32-channel
  * block, or -- for the last 16 channels of a block that is not a multiple of 32 -- two taps of 16 channels; cout_tiles 9 (blocks
  * of 144 output channels) or 7 (112).  Channel slices must split into blocks of <= 160 channels that are multiples of 16. */
@@ -116,14 +123,16 @@ typedef struct vmg_conv_desc {
   int actgrad;
   int pixel_shuffle;
   int mt;   /* 0 = auto; 16-pixel tiles per wave (1 or 2) */
-  int deep; /* kernel variant: 0 = 2-slot weight ring, 1 = 3-slot counted-wait ring, 2 = K split over the 4 waves with
-              * weights read global->register (bf16, cout_tiles <= 5, mt 1), 3 = weight-streaming 3x3 (bf16; 128-pixel tiles x 144 or
-              * 112 output channels per workgroup, loader waves stream the vmg_convws_pack image through an LDS ring; cout_tiles 9 or 7,
-              * 16-byte aligned rows, no pixel_shuffle), 4 = 1x1 with every wave its own pipeline: weights
-              * resident in registers, 16-row tiles through wave-private LDS (bf16, one dense source of <= 160 channels,
-              * cout_tiles 3 or 5, 16-byte aligned output rows), 6 = weights-stationary 3x3 (bf16, one source of <= 64 channels,
-              * cout_tiles 1, 3 or 4: a persistent workgroup per CU keeps the packed weights in LDS and walks over 128-pixel tiles;
-              * the HR head, models/vmg.py:629-632).  4 and 6 are hints: a call they do not cover runs on the general kernel */
+  int deep; /* kernel route, one of the VMG_CONV_* codes (any other value is an error):
+              * VMG_CONV_GENERAL -- the general pixel-split kernel;
+              * VMG_CONV_KSPLIT -- K split over the 4 waves, weights read global->register (bf16, cout_tiles <= 5, mt 1);
+              * VMG_CONV_WS -- weight-streaming 3x3 (bf16; 128-pixel tiles x 144 or 112 output channels per workgroup, loader waves
+              *   stream the vmg_convws_pack image through an LDS ring; cout_tiles 9 or 7, 16-byte aligned rows, no pixel_shuffle);
+              * VMG_CONV_LINEAR_WRES -- 1x1 with every wave its own pipeline: weights resident in registers, 16-row tiles through
+              *   wave-private LDS (bf16, one dense source of <= 160 channels, cout_tiles 3 or 5, 16-byte aligned output rows);
+              * VMG_CONV_WSTAT -- weights-stationary 3x3 (bf16, one source of <= 64 channels, cout_tiles 1, 3 or 4: a persistent
+              *   workgroup per CU keeps the packed weights in LDS and walks over 128-pixel tiles; the HR head, models/vmg.py:629-632).
+              * VMG_CONV_LINEAR_WRES and VMG_CONV_WSTAT are hints: a call they do not cover runs on the general kernel */
 } vmg_conv_desc;
 
 int vmg_conv_fwd(const vmg_conv_desc* d, void* stream);

@@ -262,3 +262,98 @@ def test_kernels_with_hand_counted_waits_have_no_scratch():
     assert len(hits) >= 8, f"kernel metadata not found (parsed {len(seen)} kernels)"
     bad = {k: v for k, v in hits.items() if v != 0}
     assert not bad, f"kernels with hand-counted waits that use scratch: {bad}"
+
+
+def test_pack_cache_bookkeeping():
+    """functional._PackCache driven by a fake builder on CPU tensors: a hit is the cached object; an in-place change at the same optimizer epoch
+    marks the key volatile; an epoch bump rebuilds into the old buffer; the repack plans take exactly the packs they serve; clear() drops the fp8
+    images too; settled() is the warm-up loops' old test (stamp, decay-plan stamp and -- with_repack -- the repack_all plan's stamp unmoved)."""
+    import itertools
+    from vmg_amd import functional as FH
+
+    class Img:  # what the cache reads of a K.PackedConv: .buf (rebuilt in place) and .call (weight pointer first: a plan can redo it)
+        def __init__(self, buf, call):
+            self.buf, self.call = buf, call
+
+    class Plan:  # stands in for K.PackPlan: records what it was asked to run
+        def __init__(self):
+            self.sig, self.runs = "uploaded", []
+
+        def run(self, packs, reuse=False):
+            self.runs.append((list(packs), reuse, self.sig))
+
+    builds = []
+
+    def build(key, weight, buf):
+        builds.append(buf)
+        return Img(torch.empty(16, dtype=torch.uint8) if buf is None else buf, (weight.data_ptr(),))
+
+    def build_padded(key, weight, buf):  # the pack of a zero-padded copy of the weight
+        builds.append(buf)
+        return Img(torch.empty(16, dtype=torch.uint8) if buf is None else buf, (weight.data_ptr() + 64,))
+
+    c = FH._PackCache()
+    c.stable.plan, c.vol.plan = Plan(), Plan()
+    wa, wb, wz, wq = (torch.randn(8, 8) for _ in range(4))
+
+    pa = c.get("a", wa, build)
+    assert c.stamp == 1 and builds == [None]
+    assert c.get("a", wa, build) is pa and len(builds) == 1  # hit: same object, no build
+    with torch.no_grad():
+        wa.mul_(0.5)  # in place, same epoch: the MorphFC decay case
+    pa2 = c.get("a", wa, build)
+    assert "a" in c.volatile and c.stamp == 2 and builds[-1] is pa.buf and pa2.buf is pa.buf
+
+    pb = c.get("b", wb, build)
+    s = c.stamp
+    c.bump_epoch()
+    pb2 = c.get("b", wb, build)
+    assert "b" not in c.volatile and builds[-1] is pb.buf and pb2.buf is pb.buf and c.stamp == s + 1
+    pz = c.get("z", wz, build_padded)
+    assert c.stamp == s + 1  # a padded copy's pack is not served by a plan: membership unchanged
+    pq = c.get(id(wq), wq, build, planned=False)
+    with torch.no_grad():
+        wq.add_(1.0)
+    assert c.get(id(wq), wq, build, planned=False) is not pq and id(wq) in c.q8 and id(wq) not in c.volatile and c.stamp == s + 1
+
+    c.repack_all()
+    assert c.stable.plan.runs == [([pb2], False, "uploaded")]  # neither the volatile pack nor the padded one
+    c.repack_all()
+    assert c.stable.plan.runs[-1] == ([pb2], True, "uploaded")
+    c.bump_epoch()
+    n = len(builds)
+    c.repack_all()
+    assert c.get("b", wb, build) is pb2 and len(builds) == n  # the plan's entries were marked current
+    c.decay_weights_and_repack([wa, wb], [torch.full_like(wa, 0.5), torch.full_like(wb, 0.5)])
+    assert c.vol.plan.runs == [([pa2], False, None)]  # the volatile packs of the decayed weights; sig reset for a fresh list
+    assert c.get("a", wa, build) is pa2 and c.get("z", wz, build_padded) is not pz
+
+    since = c.stamp
+    c.repack_all()
+    c.decay_weights_and_repack([wa, wb], [torch.ones_like(wa), torch.ones_like(wb)])
+    assert c.settled(since, with_repack=True) and c.settled(since, with_repack=False)
+    for st, vol, rep, since in itertools.product((3, 4), repeat=4):
+        c.stamp, c.vol.stamp, c.stable.stamp = st, vol, rep
+        assert c.settled(since, with_repack=True) == (st == since and vol == since and rep == since)
+        assert c.settled(since, with_repack=False) == (st == since and vol == since)
+
+    c.clear()
+    assert not c.ents and not c.q8 and not c.volatile
+    assert FH.clear_pack_cache == FH.PACKS.clear and FH.repack_all == FH.PACKS.repack_all
+
+
+def test_conv_fwd_refuses_unknown_routes():
+    """vmg_conv_fwd takes only the named routes (VMG_CONV_*, mirrored by hip.CONV_*): any other `deep` is an error before anything is
+    launched (the descriptor's pointers here are never dereferenced)."""
+    from vmg_amd import hip
+    l = hip.lib()
+    d = hip.ConvDesc()
+    d.dtype, d.ks, d.cout_tiles, d.N, d.H, d.W, d.Cout, d.nsrc = hip.BF16, 3, 1, 1, 1, 1, 16, 1
+    d.packed, d.out = 16, 16
+    for deep in (1, 5, 7, -1):
+        d.deep = deep
+        assert l.vmg_conv_fwd(ctypes.byref(d), None) != 0
+        assert "route" in l.vmg_last_error().decode(), deep
+    hdr = open(os.path.join(ROOT, "include", "vmg_hip.h")).read()
+    routes = {name: int(v) for name, v in re.findall(r"#define VMG_CONV_([A-Z_]+) (\d+)", hdr)}
+    assert routes == {name: getattr(hip, "CONV_" + name) for name in ("GENERAL", "KSPLIT", "WS", "LINEAR_WRES", "WSTAT")}

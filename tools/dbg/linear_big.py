@@ -8,7 +8,7 @@ for cin, cout in ((224, 224), (192, 192), (144, 144), (224, 144)):
     w = torch.randn(cout, cin, device="cuda") * cin ** -0.5
     b = torch.randn(cout, device="cuda")
     print(cin, cout, "choose_tiling:", FH.choose_tiling(M, cout, 1, torch.bfloat16, [cin]))
-    for tiles, deep, mt in ((None, 0, 1), (None, 0, 2), (None, 1, 1), (None, 1, 2), (3, 4, 1), (5, 4, 1)):
+    for tiles, deep, mt in ((None, hip.CONV_GENERAL, 1), (None, hip.CONV_GENERAL, 2), (3, hip.CONV_LINEAR_WRES, 1), (5, hip.CONV_LINEAR_WRES, 1)):
         try:
             pw = FH.packed(w, torch.bfloat16, "fwd", [cin], tiles=tiles, deep=deep)
             for _ in range(3):

@@ -20,10 +20,10 @@
 //   * the source's halo tile ((TH+2) x 18 pixels, all channels of the block) is staged once in LDS as one linear array of
 //     16-byte vectors copied by LDS-DMA; the activation operand of every k-step is a plain 16-byte LDS read at
 //     (pixel + tap offset).
-//   * packed weights stream through an LDS ring of stages filled by global_load_lds (16 B/lane, 1 KiB per
-//     instruction).  Stage images are padded to a multiple of 4 KiB so every wave issues the same number IPW of
-//     instructions and "stage s has landed" is a COUNTED s_waitcnt vmcnt((RING-2)*IPW): with 3 slots the younger
-//     stage stays in flight across the barrier.  hipcc does NOT drain LDS-DMA at __syncthreads(): the wait is explicit.
+//   * packed weights stream through a 2-slot LDS ring of stages filled by global_load_lds (16 B/lane, 1 KiB per
+//     instruction; stage images padded to a multiple of 4 KiB so every wave issues the same number IPW of instructions):
+//     the next stage is issued while the current one is computed.  hipcc does NOT drain LDS-DMA at __syncthreads():
+//     "stage s has landed" is an explicit s_waitcnt vmcnt(0) before the barrier.
 //   * MFMA: D[cout 16][pixel 16] += W[cout][k] * X[k][pixel]  (v_mfma_f32_16x16x32_bf16, or 8 x
 //     v_mfma_f32_16x16x4_f32 per k-step for fp32), so a lane ends with 4 consecutive output channels of one
 //     pixel -> 8-byte (bf16) / 16-byte (fp32) channels-last stores.
@@ -387,14 +387,14 @@ __device__ __forceinline__ void conv_epilogue_row(const ConvK& a, const f32x4 (&
   }
 }
 
-template <typename T, int KS, int MT, int NTB, bool DEEP>
+template <typename T, int KS, int MT, int NTB>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvK a) {
   constexpr int ES = ElemTraits<T>::ES, CB = ElemTraits<T>::CHUNKB;
   constexpr int TH = 4 * MT;
   constexpr int TWH = 16 + KS - 1;
   constexpr int THH = TH + KS - 1;
   constexpr int COB = NTB * 16;
-  constexpr int KSTG = kstg(KS), RING = DEEP ? 3 : 2;
+  constexpr int KSTG = kstg(KS), RING = 2;
   constexpr int SS = stage_stride(KS, NTB, CB);  // stage image size in LDS and in the packed weights
   constexpr int IPW = SS / 4096;                 // global_load_lds instructions per wave per stage
   constexpr int KK = KS * KS;
@@ -444,7 +444,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvK a) {
     const int ch = a.src_ch[s], pixb = a.src_pixb[s];
     const int CH = ch >> 3;  // 8-channel chunks of this source
     __syncthreads();         // everyone is done reading the previous halo tile
-    const bool after_restage = s > 0;  // LDS-DMA of the halo is younger than the weight stages in flight: see the stage wait
     stage_halo<T, KS, MT>(a, s, halo, n, ty, tx, m0, tid);
     __syncthreads();
 
@@ -460,9 +459,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvK a) {
     int cbk = 0, ky = 0;  // 3x3: stage = (channel block cbk, tap row ky); 1x1: stage = channel blocks 2*sl, 2*sl+1
     for (int sl = 0; sl < nst_s; ++sl, ++gst) {
       // Stage gst must have landed, and every wave must be past stage gst-1 before its slot is refilled.
-      if (RING > 2 && gst + RING - 2 < nstages && !(after_restage && sl == 0))
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RING - 2) * IPW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if (gst + RING - 1 < nstages) issue_w(gst + RING - 1);
@@ -1894,12 +1891,12 @@ int choose_pixb(int ch, int es, int cb) {
   return best;
 }
 
-template <typename T, int KS, int MT, int NTB, bool DEEP>
+template <typename T, int KS, int MT, int NTB>
 int launch_conv(const ConvK& k, int ncb, hipStream_t st) {
   constexpr int CB = ElemTraits<T>::CHUNKB;
-  const int lds = k.halo_bytes + (DEEP ? 3 : 2) * stage_stride(KS, NTB, CB);
+  const int lds = k.halo_bytes + 2 * stage_stride(KS, NTB, CB);  // halo tile + the 2-slot weight ring
   VMG_CHECK(lds <= 160 * 1024, "conv: LDS request %d B exceeds 160 KiB", lds);
-  auto fn = conv_igemm_kernel<T, KS, MT, NTB, DEEP>;
+  auto fn = conv_igemm_kernel<T, KS, MT, NTB>;
   static bool attr_set[VMG_MAX_DEVICES] = {};  // the attribute is per device (one code object per device)
   const int dev = vmg_current_device();
   if (!attr_set[dev]) {
@@ -1916,16 +1913,16 @@ int launch_conv(const ConvK& k, int ncb, hipStream_t st) {
   return 0;
 }
 
-template <typename T, int KS, int MT, bool DEEP>
+template <typename T, int KS, int MT>
 int dispatch_ntb(const ConvK& k, int ntb, int ncb, hipStream_t st) {
   switch (ntb) {
-    case 1: return launch_conv<T, KS, MT, 1, DEEP>(k, ncb, st);
-    case 3: return launch_conv<T, KS, MT, 3, DEEP>(k, ncb, st);
-    case 4: return launch_conv<T, KS, MT, 4, DEEP>(k, ncb, st);
-    case 5: return launch_conv<T, KS, MT, 5, DEEP>(k, ncb, st);
-    case 7: return launch_conv<T, KS, MT, 7, DEEP>(k, ncb, st);
-    case 8: return launch_conv<T, KS, MT, 8, DEEP>(k, ncb, st);
-    case 9: return launch_conv<T, KS, MT, 9, DEEP>(k, ncb, st);
+    case 1: return launch_conv<T, KS, MT, 1>(k, ncb, st);
+    case 3: return launch_conv<T, KS, MT, 3>(k, ncb, st);
+    case 4: return launch_conv<T, KS, MT, 4>(k, ncb, st);
+    case 5: return launch_conv<T, KS, MT, 5>(k, ncb, st);
+    case 7: return launch_conv<T, KS, MT, 7>(k, ncb, st);
+    case 8: return launch_conv<T, KS, MT, 8>(k, ncb, st);
+    case 9: return launch_conv<T, KS, MT, 9>(k, ncb, st);
   }
   vmg_set_error("conv: cout_tiles must be 1, 3, 4, 5, 7, 8 or 9 (got %d)", ntb);
   return -1;
@@ -1935,9 +1932,9 @@ int dispatch_ntb(const ConvK& k, int ntb, int ncb, hipStream_t st) {
 template <typename T>
 int dispatch_ks7(const ConvK& k, int ntb, int ncb, hipStream_t st) {
   switch (ntb) {
-    case 1: return launch_conv<T, 7, 1, 1, false>(k, ncb, st);
-    case 2: return launch_conv<T, 7, 1, 2, false>(k, ncb, st);
-    case 4: return launch_conv<T, 7, 1, 4, false>(k, ncb, st);
+    case 1: return launch_conv<T, 7, 1, 1>(k, ncb, st);
+    case 2: return launch_conv<T, 7, 1, 2>(k, ncb, st);
+    case 4: return launch_conv<T, 7, 1, 4>(k, ncb, st);
   }
   vmg_set_error("conv (7x7): cout_tiles must be 1, 2 or 4 (got %d)", ntb);
   return -1;
@@ -2254,6 +2251,9 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
   VMG_CHECK(d->packed && d->out, "conv_fwd: null packed weights / output");
   VMG_CHECK(!d->pixel_shuffle || (d->Cout % 4 == 0), "conv_fwd: pixel_shuffle needs Cout %% 4 == 0");
   VMG_CHECK(!(d->actgrad != 0 && d->aux == nullptr), "conv_fwd: actgrad without aux");
+  VMG_CHECK(d->deep == VMG_CONV_GENERAL || d->deep == VMG_CONV_KSPLIT || d->deep == VMG_CONV_WS || d->deep == VMG_CONV_LINEAR_WRES ||
+                d->deep == VMG_CONV_WSTAT,
+            "conv_fwd: unknown kernel route deep = %d", d->deep);
   const int es = d->dtype == VMG_BF16 ? 2 : 4, cbytes = es * 8;
   ConvK k;
   memset(&k, 0, sizeof(k));
@@ -2308,7 +2308,7 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
   k.nstages = kt; k.halo_bytes = (halo + 1023) & ~1023;  // the LDS-DMA copy writes whole 1-KiB pieces
   VMG_CHECK(d->out_ps >= (d->pixel_shuffle ? d->Cout / 4 : d->Cout), "conv_fwd: out pixel stride too small");
   hipStream_t st = (hipStream_t)stream;
-  if (d->deep == 3) {
+  if (d->deep == VMG_CONV_WS) {
     // weight-streaming kernel: 8 x 16 pixel tiles, dense halo, its own packed layout (vmg_convws_pack)
     VMG_CHECK(d->dtype == VMG_BF16 && d->ks == 3 && k.vec8 && (ntb == 3 || ntb == 7 || ntb == 8 || ntb == 9), "conv_fwd: the weight-streaming kernel is bf16 3x3 with 16-byte aligned rows, cout_tiles 3, 7, 8 or 9");
     for (int s = 0; s < n; ++s) VMG_CHECK(k.src_ch[s] % 16 == 0, "conv_fwd: the weight-streaming kernel takes channel blocks that are multiples of 16 (got %d)", k.src_ch[s]);
@@ -2325,7 +2325,7 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
     k.tiles_y = cdiv(d->H, 8);
     return ntb == 9 ? launch_ws<9>(k, ncb, st) : (ntb == 7 ? launch_ws<7>(k, ncb, st) : (ntb == 8 ? launch_ws<8>(k, ncb, st) : launch_ws<3>(k, ncb, st)));
   }
-  if (d->deep == 6 && d->dtype == VMG_BF16 && d->ks == 3 && mt == 1 && k.vec8 && n == 1 && (ntb == 1 || ntb == 3 || ntb == 4) && k.src_ch[0] <= 64 && k.src_ch[0] % 8 == 0 &&
+  if (d->deep == VMG_CONV_WSTAT && d->dtype == VMG_BF16 && d->ks == 3 && mt == 1 && k.vec8 && n == 1 && (ntb == 1 || ntb == 3 || ntb == 4) && k.src_ch[0] <= 64 && k.src_ch[0] % 8 == 0 &&
       k.src_ps[0] % 8 == 0 && d->W <= 255 * 16 && (long long)d->W * k.src_ps[0] * 2 * 10 < (1ll << 31)) {
     // weights-stationary kernel (a hint: anything it does not cover takes the general kernel below); its tiles are 8 rows high
     ConvK kk = k;
@@ -2340,7 +2340,7 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
       case 9: return launch_wstat<4, 2>(kk, ncb, st);
     }
   }
-  if (d->deep == 4 && d->dtype == VMG_BF16 && d->ks == 1 && k.vec8 && (ntb == 3 || ntb == 5)) {
+  if (d->deep == VMG_CONV_LINEAR_WRES && d->dtype == VMG_BF16 && d->ks == 1 && k.vec8 && (ntb == 3 || ntb == 5)) {
     // (a hint: anything it does not cover -- padded LDS stride, several sources, unaligned rows -- takes the general kernel below)
     if (n == 1 && k.src_ch[0] <= 160 && k.src_pixb[0] == k.src_ch[0] * 2) return ntb == 3 ? launch_linear_wres<3>(k, ncb, st) : launch_linear_wres<5>(k, ncb, st);
     // one wide source that the pack split into two equal blocks (288 = 2 x 144)
@@ -2349,21 +2349,16 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
       return launch_linear_wres<3, 2>(k, ncb, st);
   }
   if (d->ks == 7) return d->dtype == VMG_BF16 ? dispatch_ks7<bf16>(k, ntb, ncb, st) : dispatch_ks7<float>(k, ntb, ncb, st);
-  if (d->deep == 2) {
+  if (d->deep == VMG_CONV_KSPLIT) {
     VMG_CHECK(d->dtype == VMG_BF16 && mt == 1, "conv_fwd: the k-split variant is bf16, mt = 1");
     return d->ks == 3 ? dispatch_ksplit<bf16, 3>(k, ntb, ncb, k.halo_bytes, st) : dispatch_ksplit<bf16, 1>(k, ntb, ncb, k.halo_bytes, st);
   }
-  const bool deep = d->deep == 1;
   if (d->dtype == VMG_BF16) {
-    if (d->ks == 3) {
-      if (deep) return mt == 2 ? dispatch_ntb<bf16, 3, 2, true>(k, ntb, ncb, st) : dispatch_ntb<bf16, 3, 1, true>(k, ntb, ncb, st);
-      return mt == 2 ? dispatch_ntb<bf16, 3, 2, false>(k, ntb, ncb, st) : dispatch_ntb<bf16, 3, 1, false>(k, ntb, ncb, st);
-    }
-    if (deep) return mt == 2 ? dispatch_ntb<bf16, 1, 2, true>(k, ntb, ncb, st) : dispatch_ntb<bf16, 1, 1, true>(k, ntb, ncb, st);
-    return mt == 2 ? dispatch_ntb<bf16, 1, 2, false>(k, ntb, ncb, st) : dispatch_ntb<bf16, 1, 1, false>(k, ntb, ncb, st);
+    if (d->ks == 3) return mt == 2 ? dispatch_ntb<bf16, 3, 2>(k, ntb, ncb, st) : dispatch_ntb<bf16, 3, 1>(k, ntb, ncb, st);
+    return mt == 2 ? dispatch_ntb<bf16, 1, 2>(k, ntb, ncb, st) : dispatch_ntb<bf16, 1, 1>(k, ntb, ncb, st);
   }
-  if (d->ks == 3) return dispatch_ntb<float, 3, 1, false>(k, ntb, ncb, st);
-  return dispatch_ntb<float, 1, 1, false>(k, ntb, ncb, st);
+  if (d->ks == 3) return dispatch_ntb<float, 3, 1>(k, ntb, ncb, st);
+  return dispatch_ntb<float, 1, 1>(k, ntb, ncb, st);
 }
 
 // ------------------------------------------------------------------------------------------------ residual chains

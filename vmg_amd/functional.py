@@ -14,9 +14,6 @@ from . import hip
 from . import kernels as K
 from .hip import HipError
 
-# ---------------------------------------------------------------------------------------------------------
-# packed-weight cache: (id(param), kind, dtype, slices) -> (version, PackedConv)
-# ---------------------------------------------------------------------------------------------------------
 class _Fn(torch.autograd.Function):
     """torch.autograd.Function whose apply() skips the functorch bookkeeping (setup_context probing, dead-wrapper unwrapping of every
     argument): ~4 us per node and ~300 nodes per step on a host-bound step.  functorch transforms (vmap, functional grad) are not
@@ -27,16 +24,13 @@ class _Fn(torch.autograd.Function):
         return super(torch.autograd.Function, cls).apply(*args)
 
 
-_PACK_CACHE = {}
-
-
 def _pad_to(n: int, m: int = 8) -> int:
     return (n + m - 1) // m * m
 
 
 def choose_tiling(M: int, cout: int, ks: int, dtype: torch.dtype, src_ch: Optional[Sequence[int]] = None, pixel_shuffle: bool = False):
     """(cout_tiles, mt, deep) for a conv over M pixels.  Measured on MI355X (tools/bench_conv.py under rocprofv3, kernel
-    durations): the 144-channel 3x3 convs run best on the K-split kernel (deep = 2) as 64-pixel x 48-channel workgroups
+    durations): the 144-channel 3x3 convs run best on the K-split kernel (hip.CONV_KSPLIT) as 64-pixel x 48-channel workgroups
     (three cout blocks, no padded tile, 138 registers -> three workgroups per CU): 25 us at M = 32 768 (27 us with two
     blocks of 80; 30 us on the pixel-split kernel), 77 us at M = 114 688 (84; 96)."""
     if USE_WS and src_ch is not None and not pixel_shuffle:
@@ -45,61 +39,167 @@ def choose_tiling(M: int, cout: int, ks: int, dtype: torch.dtype, src_ch: Option
             # the recurrence of the full config (one clip per GPU: M = 2 * 64 * 64 = 8 192 pixels) has 64 of the weight-streaming kernel's 128-pixel
             # tiles for 256 CUs; the K-split kernel's 64-pixel x 64- / 48-channel workgroups fill the chip: 9.1 vs 11.4 us (112 channels), 10.9 vs
             # 14.2 us (144) at M = 8 192, 11.0 vs 11.4 / 13.2 vs 14.5 us at M = 16 384 (tools/bench_small_conv.py)
-            return (4 if cout == 112 else 3), 1, 2
+            return (4 if cout == 112 else 3), 1, hip.CONV_KSPLIT
         if t:
-            return t, 1, 3  # weight-streaming kernel: 128-pixel x 144/112-channel workgroups, the CU pulls the weights once
+            return t, 1, hip.CONV_WS  # weight-streaming kernel: 128-pixel x 144/112-channel workgroups, the CU pulls the weights once
     if dtype == torch.bfloat16 and ks == 3 and cout in (144, 288):
-        return 3, 1, 2  # 288 (local_cnn): 151 us vs 247 us at 144 -> 288, M = 114 688; the 576-channel PixelShuffle convs were slower this way
+        return 3, 1, hip.CONV_KSPLIT  # 288 (local_cnn): 151 us vs 247 us at 144 -> 288, M = 114 688; the 576-channel PixelShuffle convs were slower this way
     if dtype == torch.bfloat16 and ks == 1 and src_ch is not None and len(src_ch) == 1 and M >= 65536 and not pixel_shuffle:
         if cout == 144 and src_ch[0] == 144:
-            return 5, 1, 4  # the 144 -> 144 Linears of stage 0 (token mixers, proj): wave-autonomous kernel, 21 us vs 33 us at M = 114 688 (no gain at M = 32 768)
+            return 5, 1, hip.CONV_LINEAR_WRES  # the 144 -> 144 Linears of stage 0 (token mixers, proj): wave-autonomous kernel, 21 us vs 33 us at M = 114 688 (no gain at M = 32 768)
         if cout == 288 and src_ch[0] == 144:
-            return 5, 1, 4  # Mlp_cnn.fc2's data gradient: 39 us vs 66 us (tools/bench_linear.py)
+            return 5, 1, hip.CONV_LINEAR_WRES  # Mlp_cnn.fc2's data gradient: 39 us vs 66 us (tools/bench_linear.py)
         if cout == 144 and src_ch[0] == 288:
-            return 3, 1, 4  # Mlp_cnn.fc2 (the 288-channel source as two blocks of the pack): 48 us vs 55 us
+            return 3, 1, hip.CONV_LINEAR_WRES  # Mlp_cnn.fc2 (the 288-channel source as two blocks of the pack): 48 us vs 55 us
     if dtype == torch.bfloat16 and ks == 3 and not pixel_shuffle and M >= (1 << 18) and src_ch is not None and len(src_ch) == 1 and \
             src_ch[0] <= 64 and src_ch[0] % 8 == 0 and cout in (16, 48, 64):  # (tile counts the general kernel has too)
         # the HR head (HRconv 64 -> 64, conv_last's data gradient 8 -> 64; 1.8 M pixels): weights-stationary kernel -- one workgroup per CU keeps
         # the layer's <= 74 KiB of weights in LDS and walks over 128-pixel tiles (the general kernel re-streams them per 64-pixel workgroup)
-        return cout // 16, 1, 6
+        return cout // 16, 1, hip.CONV_WSTAT
     if dtype == torch.bfloat16 and ks == 3 and not pixel_shuffle and M >= (1 << 20) and src_ch is not None and len(src_ch) == 1 and \
             (cout <= 16 or src_ch[0] <= 16):
-        return None, 2, 0  # conv_last (64 -> 3) and its data gradient (8 -> 64) on 1.8 M pixels: 18 MFMAs per wave and tile -- 128-pixel tiles halve the workgroup count
-    return None, 1, 0
+        return None, 2, hip.CONV_GENERAL  # conv_last (64 -> 3) and its data gradient (8 -> 64) on 1.8 M pixels: 18 MFMAs per wave and tile -- 128-pixel tiles halve the workgroup count
+    return None, 1, hip.CONV_GENERAL
 
 
 USE_WS = True  # route eligible bf16 3x3 convs to the weight-streaming kernel (tests flip it to compare both)
 GROUPED_DENSE = True  # bf16 grouped 3x3 convolutions as ONE launch on the dense block-diagonal pack (tests / tools flip it to compare both)
 
-_WEIGHT_EPOCH = [0]
+# ---------------------------------------------------------------------------------------------------------
+# packed-weight cache
+# ---------------------------------------------------------------------------------------------------------
+class _PlanState:
+    """A K.PackPlan and the cache entries it rebuilds (their list is refreshed when the cache's stamp or the weight list moved)."""
+
+    def __init__(self):
+        self.plan, self.stamp, self.wkey, self.ents, self.packs = K.PackPlan(), -1, None, [], []
 
 
-def bump_weight_epoch():
-    """Invalidates every cached weight pack: called by optimizers that rewrite parameter memory outside autograd's
-    version counters (train.FlatAdamW)."""
-    _WEIGHT_EPOCH[0] += 1
+def _from_param(ent) -> bool:
+    """The pack was made from the parameter itself, not from a zero-padded copy: a PackPlan entry can redo it."""
+    pw, weight = ent[1], ent[2]
+    return pw.call is not None and pw.call[0] == weight.data_ptr()
+
+
+class _PackCache:
+    """Every cached weight image, each entry [(weight._version, epoch), pack, weight], rebuilt on demand when its weight has changed.
+
+    Packs of weights modified in place between optimizer steps (the MorphFC decay) are VOLATILE: they stay out of the one-launch repack
+    after the optimizer (repack_all) and are redone by decay_weights_and_repack instead.  `stamp` moves whenever the set of packs the
+    plans serve changes; the capture warm-up loops run until it stands still (settled)."""
+
+    def __init__(self):
+        self.ents = {}          # key -> entry
+        self.q8 = {}            # id(weight) -> entry of its fp8 image (no plan serves these: no volatile marks, no stamp)
+        self.volatile = set()   # keys of volatile packs
+        self.epoch = 0          # bumped by optimizers that rewrite parameter memory behind autograd's version counters
+        self.stamp = 0          # bumped when the set of plan-eligible packs changes (new pack, a key turned volatile, cache cleared)
+        self.stable = _PlanState()  # repack_all: every plan-eligible pack that is not volatile
+        self.vol = _PlanState()     # decay_weights_and_repack: the volatile packs of the decayed weights
+
+    def get(self, key, weight: torch.Tensor, build, planned: bool = True):
+        """The cached image under `key`, current for `weight`; on a miss build(key, weight, buf) makes it (buf: the stale image's buffer of
+        this very weight, to be rewritten in place, else None).  planned=False: the fp8 images."""
+        ents = self.ents if planned else self.q8
+        ver = (weight._version, self.epoch)
+        hit = ents.get(key)
+        buf = None
+        if hit is not None:
+            if hit[2] is weight:
+                if hit[0] == ver:
+                    return hit[1]
+                # a stale pack of this very parameter is REWRITTEN IN PLACE (stream order protects its earlier readers): its buffer's address may
+                # be baked into a captured hipGraph (the pack node and the convolutions that read it), so it must neither move nor return to the
+                # allocator while the parameter lives
+                buf = hit[1].buf
+            if planned and hit[0][1] == ver[1] and key not in self.volatile:
+                self.volatile.add(key)  # modified in place between optimizer steps (the MorphFC decay, T1): repack_all leaves it alone
+                self.stamp += 1
+        ent = [ver, build(key, weight, buf), weight]
+        if planned and key not in self.volatile and _from_param(ent):
+            self.stamp += 1  # (a new or re-created pack that repack_all serves: its plan is rebuilt)
+        ents[key] = ent
+        return ent[1]
+
+    def clear(self):
+        """Drops every cached image, the fp8 ones included."""
+        self.ents.clear()
+        self.q8.clear()
+        self.volatile.clear()
+        self.stamp += 1
+
+    def bump_epoch(self):
+        """Invalidates every cached weight pack: called by optimizers that rewrite parameter memory outside autograd's
+        version counters (train.FlatAdamW)."""
+        self.epoch += 1
+
+    def settled(self, since: int, with_repack: bool) -> bool:
+        """No pack has joined or left the plans since `stamp` read `since`, and the decay plan (with_repack: the repack_all plan too) has
+        its entry list for that membership: a captured step would upload no plan."""
+        return self.stamp == since and self.vol.stamp == since and (not with_repack or self.stable.stamp == since)
+
+    def _run_plan(self, st: _PlanState, wkey, member, reset_sig: bool = False):
+        """Rebuilds st's entry list from the cache if its membership (or the weight list wkey) moved, runs the plan in ONE launch and
+        marks its entries current."""
+        fresh = st.stamp != self.stamp or st.wkey != wkey
+        if fresh:
+            st.ents = [ent for key, ent in self.ents.items() if member(key, ent)]
+            st.packs, st.stamp, st.wkey = [ent[1] for ent in st.ents], self.stamp, wkey
+            if reset_sig:
+                st.plan.sig = None
+        if not st.packs:
+            return
+        st.plan.run(st.packs, reuse=not fresh)  # (fresh list: PackPlan compares addresses and re-uploads its entries only if they differ)
+        ep = self.epoch
+        for ent in st.ents:
+            ent[0] = (ent[2]._version, ep)
+
+    def repack_all(self):
+        """Rebuild, in ONE launch, every cached pack whose source is the parameter itself (call right after the optimizer has written the
+        parameters): the next forward finds them current instead of launching ~390 small pack kernels one by one.  The list of packs is
+        rebuilt only when the cache's membership has changed -- this runs at the very end of a step, with the GPU idle behind it."""
+        self._run_plan(self.stable, None, lambda key, ent: key not in self.volatile and _from_param(ent))
+
+    def decay_weights_and_repack(self, weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor]):
+        """W <- W * Gamma for all the given weights in ONE launch and their cached packs rebuilt in ONE more (the MorphFC retention decay of
+        every token mixer of a model, reference models/function.py:766-768 / 779-781, applied at the top of the model's forward instead of
+        module by module: 24 small multiplies and 48 pack launches per step otherwise).  Packs that are not cached yet are built on demand."""
+        with torch.no_grad():
+            torch._foreach_mul_(list(weights), list(gammas))
+        wkey = tuple(id(w) for w in weights)
+        ids = set(wkey)
+        self._run_plan(self.vol, wkey, lambda key, ent: key in self.volatile and id(ent[2]) in ids and _from_param(ent), reset_sig=True)
+
+
+PACKS = _PackCache()
+clear_pack_cache = PACKS.clear
+bump_weight_epoch = PACKS.bump_epoch
+repack_all = PACKS.repack_all
+decay_weights_and_repack = PACKS.decay_weights_and_repack
+
+
+def _pack_image(ws: bool, w: torch.Tensor, dtype: torch.dtype, **kw) -> K.PackedConv:
+    """The pack of layout 'ws' (the weight-streaming kernel's, vmg_convws_pack) or 'std' (every other route, vmg_conv_pack)."""
+    return K.pack_conv_weight_ws(w, **kw) if ws else K.pack_conv_weight(w, dtype, **kw)
 
 
 def packed(weight: torch.Tensor, dtype: torch.dtype, kind: str, src_ch: Optional[Sequence[int]] = None,
-           i0: int = 0, on: Optional[int] = None, tiles: Optional[int] = None, deep: int = 0, orange: Optional[Sequence[int]] = None,
+           i0: int = 0, on: Optional[int] = None, tiles: Optional[int] = None, deep: int = hip.CONV_GENERAL, orange: Optional[Sequence[int]] = None,
            groups: int = 1) -> K.PackedConv:
     """kind 'fwd': outputs = all O, K slices = src_ch over I (padded to multiples of 8 with zero channels when
     needed).  kind 'dgrad': outputs = I[i0:i0+on), K = all O (padded to a multiple of 8).
-    orange = (o0, no): one GROUP of a grouped convolution -- forward: only the outputs O[o0:o0+no); data gradient: K = O[o0:o0+no) (no % 8 == 0)."""
+    orange = (o0, no): one GROUP of a grouped convolution -- forward: only the outputs O[o0:o0+no); data gradient: K = O[o0:o0+no) (no % 8 == 0).
+    groups > 1: the dense block-diagonal pack of the grouped convolution's weight (_build_grouped_dense).
+    The route `deep` only decides the pack layout: the weight-streaming kernel's, or the one every other route reads."""
+    ws = deep == hip.CONV_WS
     if groups > 1:
-        return _packed_grouped_dense(weight, dtype, kind, tiles, deep, groups)
-    key = (id(weight), kind, dtype, tuple(src_ch) if src_ch else None, i0, on, tiles, deep == 3, tuple(orange) if orange else None)
-    ver = (weight._version, _WEIGHT_EPOCH[0])
-    hit = _PACK_CACHE.get(key)
-    if hit is not None and hit[0] == ver and hit[2] is weight:
-        return hit[1]
-    if hit is not None and hit[0][1] == ver[1] and key not in _PACK_VOLATILE:
-        _PACK_VOLATILE.add(key)  # modified in place between optimizer steps (the MorphFC decay, T1): repack_all leaves it alone
-        _PACK_STAMP[0] += 1
-    # a stale pack of this very parameter is REWRITTEN IN PLACE (stream order protects its earlier readers): its buffer's address may be baked
-    # into a captured hipGraph (the pack node and the convolutions that read it), so it must neither move nor return to the allocator while
-    # the parameter lives -- an eager call between replays used to re-create it and free the buffer the graph still wrote through
-    buf0 = hit[1].buf if (hit is not None and hit[2] is weight) else None
+        return PACKS.get((id(weight), kind, dtype, "dense", groups, tiles, ws), weight, _build_grouped_dense)
+    key = (id(weight), kind, dtype, tuple(src_ch) if src_ch else None, i0, on, tiles, ws, tuple(orange) if orange else None)
+    return PACKS.get(key, weight, _build_pack)
+
+
+def _build_pack(key, weight: torch.Tensor, buf: Optional[torch.Tensor]) -> K.PackedConv:
+    _, kind, dtype, src_ch, i0, on, tiles, ws, orange = key
     w = weight.detach()
     if w.dim() == 2:
         w = w[:, :, None, None]
@@ -125,133 +225,36 @@ def packed(weight: torch.Tensor, dtype: torch.dtype, kind: str, src_ch: Optional
             w = wp
             src_ch = [_pad_to(c) for c in src_ch]
         o0, no = (orange[0], orange[1]) if orange else (0, None)
-        if deep == 3:
-            pw = K.pack_conv_weight_ws(w.contiguous(), src_ch=list(src_ch), cout_tiles=tiles, o0=o0, on=no, out=buf0)
-        else:
-            pw = K.pack_conv_weight(w.contiguous(), dtype, src_ch=list(src_ch), cout_tiles=tiles, o0=o0, on=no, out=buf0)
-    elif kind == "dgrad":
+        return _pack_image(ws, w.contiguous(), dtype, src_ch=list(src_ch), cout_tiles=tiles, o0=o0, on=no, out=buf)
+    if kind == "dgrad":
         on = I - i0 if on is None else on
         if orange:
             if orange[1] % 8:
                 raise HipError("grouped data-gradient pack: the group's output channel count must be a multiple of 8")
-            if deep == 3:
-                pw = K.pack_conv_weight_ws(w.contiguous(), o0=i0, on=on, transpose_flip=True, cout_tiles=tiles, src_off=[orange[0]], src_ch=[orange[1]], out=buf0)
-            else:
-                pw = K.pack_conv_weight(w.contiguous(), dtype, o0=i0, on=on, transpose_flip=True, cout_tiles=tiles, src_off=[orange[0]], src_ch=[orange[1]], out=buf0)
-            if key not in _PACK_VOLATILE and pw.call is not None and pw.call[0] == weight.data_ptr():
-                _PACK_STAMP[0] += 1
-            _PACK_CACHE[key] = [ver, pw, weight]
-            return pw
+            return _pack_image(ws, w.contiguous(), dtype, o0=i0, on=on, transpose_flip=True, cout_tiles=tiles, src_off=[orange[0]],
+                               src_ch=[orange[1]], out=buf)
         if O % 8:
             wp = w.new_zeros(_pad_to(O), *w.shape[1:])
             wp[:O].add_(w)  # (an add kernel into the zeros: a contiguous copy_ would be a memcpy node, see the forward pack)
             w = wp
-        if deep == 3:
-            pw = K.pack_conv_weight_ws(w.contiguous(), o0=i0, on=on, transpose_flip=True, cout_tiles=tiles, out=buf0)
-        else:
-            pw = K.pack_conv_weight(w.contiguous(), dtype, o0=i0, on=on, transpose_flip=True, cout_tiles=tiles, out=buf0)
-    else:
-        raise HipError(kind)
-    if key not in _PACK_VOLATILE and pw.call is not None and pw.call[0] == weight.data_ptr():
-        _PACK_STAMP[0] += 1  # (a new or re-created pack that repack_all serves: its plan is rebuilt; packs of zero-padded copies and of
-        #                       weights modified in place are redone on demand every step and never enter the plan)
-    _PACK_CACHE[key] = [ver, pw, weight]
-    return pw
+        return _pack_image(ws, w.contiguous(), dtype, o0=i0, on=on, transpose_flip=True, cout_tiles=tiles, out=buf)
+    raise HipError(kind)
 
 
-def _packed_grouped_dense(weight: torch.Tensor, dtype: torch.dtype, kind: str, tiles: Optional[int], deep: int, groups: int) -> K.PackedConv:
+def _build_grouped_dense(key, weight: torch.Tensor, buf: Optional[torch.Tensor]) -> K.PackedConv:
     """The dense block-diagonal pack of a grouped convolution's weight (O, cg, ks, ks): 'fwd' = all O outputs over groups * cg input channels,
     'dgrad' = all groups * cg outputs over K = O (multiples of 8).  Built from the parameter itself by the pack kernels (no dense copy), so it is
     served by the one-launch repack like any other pack."""
-    key = (id(weight), kind, dtype, "dense", groups, tiles, deep == 3)
-    ver = (weight._version, _WEIGHT_EPOCH[0])
-    hit = _PACK_CACHE.get(key)
-    if hit is not None and hit[0] == ver and hit[2] is weight:
-        return hit[1]
-    buf0 = hit[1].buf if (hit is not None and hit[2] is weight) else None
+    _, kind, dtype, _, groups, tiles, ws = key
     w = weight.detach().contiguous()
     O, cg = w.shape[0], w.shape[1]
     if kind == "fwd":
-        args = dict(src_ch=[cg * groups], cout_tiles=tiles, groups=groups, out=buf0)
-    elif kind == "dgrad":
+        return _pack_image(ws, w, dtype, src_ch=[cg * groups], cout_tiles=tiles, groups=groups, out=buf)
+    if kind == "dgrad":
         if O % 8:
             raise HipError("grouped dense data-gradient pack: output channels must be a multiple of 8")
-        args = dict(transpose_flip=True, cout_tiles=tiles, groups=groups, out=buf0)
-    else:
-        raise HipError(kind)
-    pw = K.pack_conv_weight_ws(w, **args) if deep == 3 else K.pack_conv_weight(w, dtype, **args)
-    if pw.call is not None and pw.call[0] == weight.data_ptr():
-        _PACK_STAMP[0] += 1
-    _PACK_CACHE[key] = [ver, pw, weight]
-    return pw
-
-
-def clear_pack_cache():
-    _PACK_CACHE.clear()
-    _PACK_VOLATILE.clear()
-    _PACK_STAMP[0] += 1
-
-
-_PACK_VOLATILE = set()
-_PACK_PLAN = K.PackPlan()
-
-
-_PACK_STAMP = [0]   # bumped when the set of plan-eligible packs changes (new key, a key turned volatile, cache cleared)
-_PACK_STATE = {"stamp": -1, "ents": [], "packs": []}
-
-
-def repack_all():
-    """Rebuild, in ONE launch, every cached pack whose source is the parameter itself (call right after the optimizer has written the
-    parameters): the next forward finds them current instead of launching ~390 small pack kernels one by one.  The list of packs is
-    rebuilt only when the cache's membership has changed -- this runs at the very end of a step, with the GPU idle behind it."""
-    st = _PACK_STATE
-    if st["stamp"] != _PACK_STAMP[0]:
-        ents, packs = [], []
-        for key, ent in _PACK_CACHE.items():
-            pw, weight = ent[1], ent[2]
-            if key in _PACK_VOLATILE or pw.call is None or pw.call[0] != weight.data_ptr():
-                continue  # (a zero-padded copy was packed, not the parameter: the on-demand path redoes it)
-            ents.append(ent)
-            packs.append(pw)
-        fresh = True
-        st["ents"], st["packs"], st["stamp"] = ents, packs, _PACK_STAMP[0]
-    else:
-        fresh = False
-    if not st["packs"]:
-        return
-    _PACK_PLAN.run(st["packs"], reuse=not fresh)  # (fresh list: PackPlan compares addresses and re-uploads its entries only if they differ)
-    ep = _WEIGHT_EPOCH[0]
-    for ent in st["ents"]:
-        ent[0] = (ent[2]._version, ep)
-
-
-_VOL_PLAN = K.PackPlan()
-_VOL_STATE = {"stamp": -1, "wkey": None, "ents": [], "packs": []}
-
-
-def decay_weights_and_repack(weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor]):
-    """W <- W * Gamma for all the given weights in ONE launch and their cached packs rebuilt in ONE more (the MorphFC retention decay of every
-    token mixer of a model, reference models/function.py:766-768 / 779-781, applied at the top of the model's forward instead of module by
-    module: 24 small multiplies and 48 pack launches per step otherwise).  Packs that are not cached yet are built on demand as before."""
-    with torch.no_grad():
-        torch._foreach_mul_(list(weights), list(gammas))
-    st = _VOL_STATE
-    wkey = tuple(id(w) for w in weights)
-    if st["stamp"] != _PACK_STAMP[0] or st["wkey"] != wkey:
-        ids = set(wkey)
-        ents = [ent for key, ent in _PACK_CACHE.items()
-                if key in _PACK_VOLATILE and id(ent[2]) in ids and ent[1].call is not None and ent[1].call[0] == ent[2].data_ptr()]
-        st["ents"], st["packs"], st["stamp"], st["wkey"] = ents, [e[1] for e in ents], _PACK_STAMP[0], wkey
-        _VOL_PLAN.sig = None
-        fresh = True
-    else:
-        fresh = False
-    if not st["packs"]:
-        return
-    _VOL_PLAN.run(st["packs"], reuse=not fresh)
-    ep = _WEIGHT_EPOCH[0]
-    for ent in st["ents"]:
-        ent[0] = (ent[2]._version, ep)
+        return _pack_image(ws, w, dtype, transpose_flip=True, cout_tiles=tiles, groups=groups, out=buf)
+    raise HipError(kind)
 
 
 def _pad_channels(t: torch.Tensor, mult: int = 8) -> torch.Tensor:
@@ -564,7 +567,7 @@ class _Conv2d(_Fn):
         if pixel_shuffle and USE_WS and res is None:
             t_ws = K.ws_eligible(weight.shape[0], ks, dt, [s.shape[-1] for s in srcs_p])
             if t_ws:
-                ps_after, tiles, mt, deep = True, t_ws, 1, 3
+                ps_after, tiles, mt, deep = True, t_ws, 1, hip.CONV_WS
         pw = packed(weight, dt, "fwd", src_ch, tiles=tiles, deep=deep)
         need_pre = act == hip.ACT_GELU and any(ctx.needs_input_grad)
         out, pre = K.conv_forward(srcs_p, pw, bias, N, H, W, act=act, slope=slope, alpha=alpha, res=res,
@@ -687,7 +690,7 @@ class _GroupedConv2d(_Fn):
         og, dt, M = O // G, x.dtype, N * H * W
         ctx.x_shape = tuple(x.shape)
         x = x.contiguous()
-        # Round 4: ALL groups as ONE launch on the dense block-diagonal pack (functional._packed_grouped_dense) -- G times the multiplies, a
+        # Round 4: ALL groups as ONE launch on the dense block-diagonal pack (functional._build_grouped_dense) -- G times the multiplies, a
         # G-th of the launches, and full-width channel vectors instead of 28- / 56-channel slices: at the full configuration's stage sizes (7 x 64^2
         # .. 7 x 8^2 pixels) the grouped launches were latency-, not FLOP-bound (profiles/r04_a_full_step_kernels.txt).  bf16, 3x3, C and O multiples of 8.
         # (measured, tools/bench_grouped_conv.py, forward + backward: 412 -> 305 us at 7 x 64^2 x 112 ch, 334 -> 308 at 32^2 x 224, 329 -> 252 at 16^2 x 224,
@@ -791,7 +794,6 @@ def grouped_conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
 # ---- fp8 chains: conv1 / conv2 of every residual block on the block-scaled fp8 kernel (csrc/conv_fp8.hip) ----------------------
 FP8_CHAINS = False          # process-wide default (set_fp8_chains); VMG(fp8_chains=True) switches it on per model
 FP8_STATS = {"chains": 0}   # forward chains that ran on the fp8 kernel (tests)
-_Q8_CACHE = {}
 
 
 def set_fp8_chains(on: bool):
@@ -801,13 +803,11 @@ def set_fp8_chains(on: bool):
 
 def packed_q8(weight: torch.Tensor) -> K.PackedQ8:
     """The fp8 weight image of a 3x3 convolution, cached per parameter version / optimizer epoch (rebuilt on demand: two small launches)."""
-    ver = (weight._version, _WEIGHT_EPOCH[0])
-    hit = _Q8_CACHE.get(id(weight))
-    if hit is not None and hit[0] == ver and hit[2] is weight:
-        return hit[1]
-    pw = K.pack_conv_weight_q8(weight.detach().contiguous(), out=hit[1].buf if (hit is not None and hit[2] is weight) else None)
-    _Q8_CACHE[id(weight)] = (ver, pw, weight)
-    return pw
+    return PACKS.get(id(weight), weight, _build_q8, planned=False)
+
+
+def _build_q8(key, weight: torch.Tensor, buf: Optional[torch.Tensor]) -> K.PackedQ8:
+    return K.pack_conv_weight_q8(weight.detach().contiguous(), out=buf)
 
 
 def _chain_forward_fp8(srcs, params, r_scaling, keep_t: bool):

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("VMG_HIP_LIB") or os.path.join(HERE, "libvmg_hip.so") 
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_GELU = 0, 1, 2, 3
+# conv kernel routes (ConvDesc.deep, include/vmg_hip.h VMG_CONV_*)
+CONV_GENERAL, CONV_KSPLIT, CONV_WS, CONV_LINEAR_WRES, CONV_WSTAT = 0, 2, 3, 4, 6
 
 
 class HipError(RuntimeError):

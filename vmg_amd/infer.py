@@ -55,9 +55,9 @@ class GraphedModel:
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for i in range(max(self.warmup, 6)):  # until the cached weight packs / repack plans have settled (see train.TrainStep.capture)
-                    stamp = FH._PACK_STAMP[0]
+                    stamp = FH.PACKS.stamp
                     self.model(static_in)
-                    if i + 1 >= self.warmup and FH._PACK_STAMP[0] == stamp and FH._VOL_STATE["stamp"] == stamp:
+                    if i + 1 >= self.warmup and FH.PACKS.settled(stamp, with_repack=False):
                         break
                 for w, s0 in zip(ws, saved):
                     w.copy_(s0)

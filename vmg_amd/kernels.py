@@ -45,7 +45,7 @@ class PackedConv:
 
     def __init__(self, buf, dtype, ks, cout, src_ch, cout_tiles, layout="std", call=None):
         self.buf, self.dtype, self.ks, self.cout, self.src_ch, self.cout_tiles = buf, dtype, ks, cout, list(src_ch), cout_tiles
-        self.layout = layout  # 'std': vmg_conv_pack; 'ws': vmg_convws_pack (the weight-streaming 3x3 kernel, deep = 3)
+        self.layout = layout  # 'std': vmg_conv_pack; 'ws': vmg_convws_pack (the weight-streaming 3x3 kernel, route hip.CONV_WS)
         self.call = call      # (weight data_ptr, O, I, o0, on, src_off, src_ch, transpose_flip): what a plan entry needs to redo this pack
 
 
@@ -179,7 +179,7 @@ def conv_forward(srcs: Sequence[torch.Tensor], pw: PackedConv, bias: Optional[to
                  act: int = hip.ACT_NONE, slope: float = 0.0, alpha: float = 1.0, res: Optional[torch.Tensor] = None,
                  aux: Optional[torch.Tensor] = None, actgrad: int = 0, pixel_shuffle: bool = False,
                  out: Optional[torch.Tensor] = None, out_pre: Optional[torch.Tensor] = None, want_pre: bool = False,
-                 mt: int = 0, deep: int = 0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                 mt: int = 0, deep: int = hip.CONV_GENERAL) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Runs vmg_conv_fwd.  srcs: channels-last tensors (..., C_s) covering N*H*W pixels each (channel slices of
     wider tensors are fine).  Returns (out, out_pre)."""
     if len(srcs) != len(pw.src_ch):
@@ -191,8 +191,8 @@ def conv_forward(srcs: Sequence[torch.Tensor], pw: PackedConv, bias: Optional[to
         raise HipError(f"activation dtype {dt} != packed weight dtype {pw.dtype}")
     M = N * H * W
     nsrc = len(srcs)
-    if (pw.layout == "ws") != (deep == 3):
-        deep = 3 if pw.layout == "ws" else 0  # the packed layout decides the kernel
+    if (pw.layout == "ws") != (deep == hip.CONV_WS):
+        deep = hip.CONV_WS if pw.layout == "ws" else hip.CONV_GENERAL  # the packed layout decides the kernel
     sp, sps, sch = [0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0]
     for i, s in enumerate(srcs):
         if s.dtype != dt or s.shape[-1] != pw.src_ch[i] or s.numel() // s.shape[-1] != M:
@@ -243,7 +243,7 @@ def _parr(ts):
     return (ctypes.c_void_p * max(1, len(ts)))(*[(t.data_ptr() if t is not None else None) for t in ts])
 
 
-CHAIN_STATS = {"fwd": {}, "bwd": {}}  # chain calls by the `deep` route their block convolutions took (3: weight-streaming, 2: K-split, ...): read by tests
+CHAIN_STATS = {"fwd": {}, "bwd": {}}  # chain calls by the route (hip.CONV_*) their block convolutions took: read by tests
 
 
 def resblock_chain_forward(srcs: Sequence[torch.Tensor], pw0: PackedConv, b0: torch.Tensor, slope0: float, deep0: int, pw1: Sequence[PackedConv],
@@ -273,12 +273,12 @@ def resblock_chain_forward(srcs: Sequence[torch.Tensor], pw0: PackedConv, b0: to
     for i, s in enumerate(srcs):
         d.src[i], d.src_ps[i], d.src_ch[i] = s.data_ptr(), _pix_stride(s), pw0.src_ch[i]
     d.packed0, d.bias0, d.slope0 = pw0.buf.data_ptr(), b0.data_ptr(), slope0
-    d.cout_tiles0, d.deep0 = pw0.cout_tiles, 3 if pw0.layout == "ws" else deep0
+    d.cout_tiles0, d.deep0 = pw0.cout_tiles, hip.CONV_WS if pw0.layout == "ws" else deep0
     keep = [_parr([p.buf for p in pw1]), _parr(list(b1)), _parr([p.buf for p in pw2]), _parr(list(b2)), _parr(ys), _parr(ts)]
     d.packed1, d.bias1, d.packed2, d.bias2, d.y, d.t = keep
     d.r_scaling = r_scaling
     d.cout_tiles = pw1[0].cout_tiles if nblk else pw0.cout_tiles
-    d.deep = (3 if pw1[0].layout == "ws" else deep) if nblk else 0
+    d.deep = (hip.CONV_WS if pw1[0].layout == "ws" else deep) if nblk else hip.CONV_GENERAL
     hip.check(hip.lib().vmg_resblock_chain_fwd(ctypes.byref(d), hip.stream_ptr()), "vmg_resblock_chain_fwd")
     CHAIN_STATS["fwd"][d.deep] = CHAIN_STATS["fwd"].get(d.deep, 0) + 1
     return ys, ts
@@ -302,7 +302,7 @@ def resblock_chain_backward(g: torch.Tensor, ts: Sequence[torch.Tensor], pd1: Se
     d.packed1, d.packed2, d.t, d.g_y, d.g_t = keep
     d.r_scaling = r_scaling
     d.cout_tiles = pd1[0].cout_tiles
-    d.deep = 3 if pd1[0].layout == "ws" else deep
+    d.deep = hip.CONV_WS if pd1[0].layout == "ws" else deep
     hip.check(hip.lib().vmg_resblock_chain_bwd(ctypes.byref(d), hip.stream_ptr()), "vmg_resblock_chain_bwd")
     CHAIN_STATS["bwd"][d.deep] = CHAIN_STATS["bwd"].get(d.deep, 0) + 1
     return gys, gts

@@ -628,9 +628,9 @@ class TrainStep:
             # MorphFC decay) is recognised in the SECOND step and joins the one-launch repack plans in the third; a plan that is rebuilt inside
             # the capture would upload its entries there (a host-to-device copy: not capturable)
             for i in range(max(warmup, 8)):
-                stamp = FH._PACK_STAMP[0]
+                stamp = FH.PACKS.stamp
                 self._eager(*self._static)
-                if i + 1 >= warmup and FH._PACK_STAMP[0] == stamp and FH._VOL_STATE["stamp"] == stamp and FH._PACK_STATE["stamp"] == stamp:
+                if i + 1 >= warmup and FH.PACKS.settled(stamp, with_repack=True):
                     break
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
