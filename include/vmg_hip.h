@@ -265,7 +265,7 @@ int vmg_linear_wgrad2_multi(int nprob, int npairs, const void* const* x, const v
  * vmg_layernorm_fwd  y = (x - mean) * rstd * w + b over the last dim C of (M, C) rows, eps inside the sqrt; mean / rstd
  *                    (fp32, M each) are written when non-null.  nn.LayerNorm at function.py:1164,1195; layers.py:768-775;
  *                    swin_3d.py:717,741.
- * vmg_layernorm_bwd  dx, and dw += sum dy * xhat, db += sum dy (fp32 atomics).
+ * vmg_layernorm_bwd  dx, and dw += sum dy * xhat, db += sum dy (fp32 atomics); prototype and workspace contract below.
  * ---------------------------------------------------------------------------------------------- */
 int vmg_act_bwd(int dtype, const void* dy, const void* ref, void* out, int64_t n, int act, float slope, float alpha,
                 void* stream);
@@ -279,27 +279,28 @@ int vmg_pixel_unshuffle_actgrad(int dtype, const void* dy, const void* ref, void
                                 float alpha, void* stream);
 int vmg_layernorm_fwd(int dtype, const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int64_t M,
                       int C, float eps, void* stream);
-int vmg_layernorm_bwd(int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* w, void* dx,
-                      float* dw, float* db, int64_t M, int C, void* stream);
-/* the same with dx = add + LayerNorm backward (add: contiguous (M, C) in the activation dtype, or null): the gradient that reaches the
- * normalised tensor through a skip connection (TAB: x feeds norm2 / norm3 AND the residual, models/function.py:1212-1217) is summed here
- * instead of by a separate pass */
-int vmg_layernorm_bwd_add(int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* w, const void* add,
-                          void* dx, float* dw, float* db, int64_t M, int C, void* stream);
-/* The same with ndy (1..5) gradients of the LayerNorm OUTPUT, summed in fp32 inside the kernel (a normalised tensor read by several consumers --
- * the MorphFC mixer reads LayerNorm(x) five times -- gets one gradient per consumer; autograd would add them pairwise, three passes per add). */
-int vmg_layernorm_bwd_multi(int dtype, int ndy, const void* const* dy, const void* x, const float* mean, const float* rstd, const float* w,
-                            const void* add, void* dx, float* dw, float* db, int64_t M, int C, void* stream);
+/* LayerNorm backward: dx = [add +] the input gradient for the SUM of ndy (1..5) gradients dy[i] of the LayerNorm output; dw / db are added to.
+ *   dy[i]  contiguous (M, C) rows, 16-byte aligned; summed in fp32 inside the kernel (a normalised tensor read by several consumers -- the
+ *          MorphFC mixer reads LayerNorm(x) five times -- gets one gradient per consumer; autograd would add them pairwise, three passes per add).
+ *   add    contiguous (M, C) in the activation dtype, 16-byte aligned, or null: the gradient that reaches the normalised tensor through a skip
+ *          connection (TAB: x feeds norm2 / norm3 AND the residual, models/function.py:1212-1217) is summed here instead of by a separate pass.
+ *   ws     null, or vmg_layernorm_bwd_ws_bytes() bytes of device memory, 16-byte aligned, ALL ZERO before its first use.  Every launch leaves it
+ *          all zero again, so one buffer serves every call; all launches that share a workspace must be ordered on one stream.  With a
+ *          workspace a grid of more than 32 blocks (C <= 2048) sums dw / db through 32 sub-accumulators; without one (and for smaller
+ *          grids, which ignore it) every block adds to dw / db with plain float atomics -- same result up to summation order, slower on large grids. */
+int64_t vmg_layernorm_bwd_ws_bytes(void);
+int vmg_layernorm_bwd(int dtype, int ndy, const void* const* dy, const void* x, const float* mean, const float* rstd, const float* w,
+                      const void* add, void* dx, float* dw, float* db, int64_t M, int C, void* ws, void* stream);
 
 /* ---- UpdownkeepSampling (reference: models/layers.py:777-798): the space<->depth rearrangement fused into the LayerNorm that follows it.
  * The LayerNorm rows are GATHERED from the feature map (forward) and their gradient is scattered back (backward); no rearranged
  * copy exists.  mode 1 = "down" ('n d c (h neih) (w neiw) -> n d h w (neiw neih c)': x is (N, 2H, 2W, cseg), rows (N*H*W, 4*cseg));
  * mode 2 = "up" ('n d (neiw neih c) h w -> n d (h neih) (w neiw) c': x is (N, H/2, W/2, 4*cseg), rows (N*H*W, cseg)).  y, dy: contiguous rows;
- * the Linear of the module is vmg_conv_fwd (KS = 1) on y.  w, b, mean, rstd, dw, db as in vmg_layernorm_fwd / _bwd. */
+ * the Linear of the module is vmg_conv_fwd (KS = 1) on y.  w, b, mean, rstd, dw, db, ws as in vmg_layernorm_fwd / _bwd. */
 int vmg_space_depth_ln_fwd(int dtype, int mode, const void* x, const float* w, const float* b, void* y, float* mean, float* rstd, int N, int H,
                            int W, int cseg, float eps, void* stream);
 int vmg_space_depth_ln_bwd(int dtype, int mode, const void* dy, const void* x, const float* mean, const float* rstd, const float* w, void* dx,
-                           float* dw, float* db, int N, int H, int W, int cseg, void* stream);
+                           float* dw, float* db, int N, int H, int W, int cseg, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * TAB token-mixer tail (models/function.py:542-558 channel attention, :791-802 branch re-weighting + tanh gate).

@@ -357,3 +357,30 @@ def test_conv_fwd_refuses_unknown_routes():
     hdr = open(os.path.join(ROOT, "include", "vmg_hip.h")).read()
     routes = {name: int(v) for name, v in re.findall(r"#define VMG_CONV_([A-Z_]+) (\d+)", hdr)}
     assert routes == {name: getattr(hip, "CONV_" + name) for name in ("GENERAL", "KSPLIT", "WS", "LINEAR_WRES", "WSTAT")}
+
+
+def test_native_library_never_allocates_or_synchronises():
+    """include/vmg_hip.h: "kernels are enqueued, never synchronised; no allocation happens inside".  No source of the library calls the
+    allocator, a device-wide synchronise or the synchronous memset (hipMemsetAsync on the caller's stream is fine)."""
+    csrc = os.path.join(ROOT, "vmg_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, f)).read()
+        for banned in ("hipMalloc", "hipFree(", "hipDeviceSynchronize", "hipMemset("):
+            assert banned not in src, f"{f} calls {banned}"
+
+
+def test_layernorm_bwd_workspace_size_and_argument_checks():
+    """The LayerNorm backward's workspace is the caller's: its size is a positive multiple of 16 bytes, and vmg_layernorm_bwd refuses a
+    gradient count outside 1..5 and a misaligned skip gradient before anything is launched (the pointers here are never dereferenced)."""
+    from vmg_amd import hip
+    l = hip.lib()
+    nbytes = l.vmg_layernorm_bwd_ws_bytes()
+    assert nbytes > 0 and nbytes % 16 == 0
+
+    def call(ndy, add):
+        dys = (ctypes.c_void_p * 6)(*[16] * 6)
+        return l.vmg_layernorm_bwd(hip.BF16, ndy, dys, 16, 16, 16, 16, add, 16, 16, 16, 64, 16, None, None)
+
+    for ndy, add, what in ((0, None, "1 to 5"), (6, None, "1 to 5"), (1, 24, "add must be 16-byte aligned")):
+        assert call(ndy, add) != 0
+        assert what in l.vmg_last_error().decode(), (ndy, add)

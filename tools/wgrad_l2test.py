@@ -25,7 +25,7 @@ dw = torch.zeros(C, C, 3, 3, device="cuda")
 db = torch.zeros(C, device="cuda")
 l = K.hip.lib()
 import ctypes
-ws = K._wgrad_workspace(dw.device)
+ws = K._workspace("vmg_conv_wgrad_ws_bytes", dw.device)
 xa = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in xs])
 da = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in dys])
 for _ in range(20):

@@ -465,27 +465,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
   if (threadIdx.x == 0) atomicExch(counter, 0u);  // ready for the next launch on this stream
 }
 
-// per-device workspace of the backward's sub-accumulators (zero between launches) + the arrival counter: allocated on the first call outside a
-// stream capture.  One per device: LayerNorm backward launches of a device must be stream-ordered (autograd runs them on the forward's stream).
-static float* g_ln_ws[VMG_MAX_DEVICES] = {};
-static unsigned int* g_ln_counter[VMG_MAX_DEVICES] = {};
+// workspace of the backward's sub-accumulators (zero between launches) + the arrival counter.  The caller owns it (vmg_hip.h): launches that
+// share one must be stream-ordered (autograd runs a device's LayerNorm backwards on the forward's stream).
 constexpr size_t LN_WS_FLOATS = (size_t)LN_SUB * 2 * 2048;  // C <= 64 lanes * LN_MAXV vectors * 8 = 2048
-static float* ln_workspace(hipStream_t st, unsigned int** counter) {
-  const int dev = vmg_current_device();
-  if (!g_ln_ws[dev]) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
-    char* p = nullptr;
-    if (hipMalloc((void**)&p, LN_WS_FLOATS * 4 + 64) != hipSuccess || hipMemset(p, 0, LN_WS_FLOATS * 4 + 64) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    g_ln_ws[dev] = reinterpret_cast<float*>(p);
-    g_ln_counter[dev] = reinterpret_cast<unsigned int*>(p + LN_WS_FLOATS * 4);
-  }
-  *counter = g_ln_counter[dev];
-  return g_ln_ws[dev];
-}
+extern "C" int64_t vmg_layernorm_bwd_ws_bytes(void) { return (int64_t)(LN_WS_FLOATS * 4 + 64); }
 
 // lanes per row: the G in {16, 32, 64} that wastes the fewest lane slots (G * ceil(nvec / G)), the smaller G on a tie -- more rows per
 // block and more vectors (= loads in flight) per lane: C = 144 bf16 (18 vectors) runs on 16 lanes x 2 vectors, not 32 x 1
@@ -792,7 +775,7 @@ static int ln_fwd_t(const void* x, const float* w, const float* b, void* y, floa
 
 template <typename T, int V>
 static int ln_bwd_t(const void* dy, const void* x, const float* mean, const float* rstd, const float* w, void* dx, float* dw, float* db,
-                    long long M, int C, hipStream_t st, const LnMap map, const void* add, const LnMore more) {
+                    long long M, int C, void* caller_ws, hipStream_t st, const LnMap map, const void* add, const LnMore more) {
   const int nvec = C / V;
   const int G = ln_group(nvec);
   VMG_CHECK(nvec <= G * LN_MAXV, "layernorm: C = %d too large", C);
@@ -804,8 +787,8 @@ static int ln_bwd_t(const void* dy, const void* x, const float* mean, const floa
 #endif
   const int lds = 8 * C * 4;  // [4 waves][2][C] floats
   const int nv = (nvec + G - 1) / G;
-  unsigned int* counter = nullptr;
-  float* ws = (blocks > LN_SUB && C <= 2048) ? ln_workspace(st, &counter) : nullptr;  // (null: plain float atomics on dw / db)
+  float* ws = (blocks > LN_SUB && C <= 2048) ? static_cast<float*>(caller_ws) : nullptr;  // (null: plain float atomics on dw / db)
+  unsigned int* counter = ws ? reinterpret_cast<unsigned int*>(ws + LN_WS_FLOATS) : nullptr;
 #define LN_LAUNCH_M(GG, NV, MP, SP) hipLaunchKernelGGL((layernorm_bwd_kernel<T, V, GG, NV, MP, SP>), dim3(blocks), dim3(256), lds, st, (const T*)dy, (const T*)x, mean, rstd, w, (T*)dx, dw, db, M, C, map, (const T*)add, ws, counter, more)
 #define LN_LAUNCH(GG, NV) do { \
     if (map.mode != 0) LN_LAUNCH_M(GG, NV, true, 0); \
@@ -876,54 +859,36 @@ extern "C" int vmg_space_depth_ln_fwd(int dtype, int mode, const void* x, const 
 }
 
 static int ln_bwd_impl(int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* w, void* dx, float* dw,
-                       float* db, int64_t M, int C, void* stream, const LnMap map, int vmax, const void* add = nullptr, const LnMore more = LnMore{{nullptr, nullptr, nullptr, nullptr}, 0}) {
+                       float* db, int64_t M, int C, void* ws, void* stream, const LnMap map, int vmax, const void* add = nullptr,
+                       const LnMore more = LnMore{{nullptr, nullptr, nullptr, nullptr}, 0}) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "layernorm_bwd: bad dtype");
   VMG_CHECK(dy && x && mean && rstd && w && dx && dw && db && M > 0 && C > 0, "layernorm_bwd: bad arguments");
+  VMG_CHECK((uintptr_t)ws % 16 == 0, "layernorm_bwd: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   int v = ln_vec(dtype, C);
   while (v > vmax) v >>= 1;
-  if (dtype == VMG_BF16) {
-    switch (v) {
-      case 8: return ln_bwd_t<bf16, 8>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-      case 4: return ln_bwd_t<bf16, 4>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-      case 2: return ln_bwd_t<bf16, 2>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-      default: return ln_bwd_t<bf16, 1>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-    }
-  }
-  switch (v) {
-    case 4: return ln_bwd_t<float, 4>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-    case 2: return ln_bwd_t<float, 2>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-    default: return ln_bwd_t<float, 1>(dy, x, mean, rstd, w, dx, dw, db, M, C, st, map, add, more);
-  }
+#define LN_BWD(T, V) ln_bwd_t<T, V>(dy, x, mean, rstd, w, dx, dw, db, M, C, ws, st, map, add, more)
+  if (dtype == VMG_BF16) return v == 8 ? LN_BWD(bf16, 8) : v == 4 ? LN_BWD(bf16, 4) : v == 2 ? LN_BWD(bf16, 2) : LN_BWD(bf16, 1);
+  return v == 4 ? LN_BWD(float, 4) : v == 2 ? LN_BWD(float, 2) : LN_BWD(float, 1);
+#undef LN_BWD
 }
 
-extern "C" int vmg_layernorm_bwd(int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* w,
-                                 void* dx, float* dw, float* db, int64_t M, int C, void* stream) {
-  return ln_bwd_impl(dtype, dy, x, mean, rstd, w, dx, dw, db, M, C, stream, LnMap{0, 0, 0, 0}, 8);
-}
-
-extern "C" int vmg_layernorm_bwd_add(int dtype, const void* dy, const void* x, const float* mean, const float* rstd, const float* w,
-                                     const void* add, void* dx, float* dw, float* db, int64_t M, int C, void* stream) {
-  VMG_CHECK(!add || (uintptr_t)add % 16 == 0, "layernorm_bwd_add: add must be 16-byte aligned");
-  return ln_bwd_impl(dtype, dy, x, mean, rstd, w, dx, dw, db, M, C, stream, LnMap{0, 0, 0, 0}, 8, add);
-}
-
-extern "C" int vmg_layernorm_bwd_multi(int dtype, int ndy, const void* const* dy, const void* x, const float* mean, const float* rstd, const float* w,
-                                       const void* add, void* dx, float* dw, float* db, int64_t M, int C, void* stream) {
-  VMG_CHECK(dy && ndy >= 1 && ndy <= 5, "layernorm_bwd_multi: 1 to 5 output gradients");
+extern "C" int vmg_layernorm_bwd(int dtype, int ndy, const void* const* dy, const void* x, const float* mean, const float* rstd, const float* w,
+                                 const void* add, void* dx, float* dw, float* db, int64_t M, int C, void* ws, void* stream) {
+  VMG_CHECK(dy && ndy >= 1 && ndy <= 5, "layernorm_bwd: 1 to 5 output gradients");
   LnMore more{{nullptr, nullptr, nullptr, nullptr}, ndy - 1};
   for (int i = 0; i < ndy; ++i) {
-    VMG_CHECK(dy[i] && (uintptr_t)dy[i] % 16 == 0, "layernorm_bwd_multi: gradient %d is null or not 16-byte aligned", i);
+    VMG_CHECK(dy[i] && (uintptr_t)dy[i] % 16 == 0, "layernorm_bwd: gradient %d is null or not 16-byte aligned", i);
     if (i) more.p[i - 1] = dy[i];
   }
-  VMG_CHECK(!add || (uintptr_t)add % 16 == 0, "layernorm_bwd_multi: add must be 16-byte aligned");
-  return ln_bwd_impl(dtype, dy[0], x, mean, rstd, w, dx, dw, db, M, C, stream, LnMap{0, 0, 0, 0}, 8, add, more);
+  VMG_CHECK(!add || (uintptr_t)add % 16 == 0, "layernorm_bwd: add must be 16-byte aligned");
+  return ln_bwd_impl(dtype, dy[0], x, mean, rstd, w, dx, dw, db, M, C, ws, stream, LnMap{0, 0, 0, 0}, 8, add, more);
 }
 
 extern "C" int vmg_space_depth_ln_bwd(int dtype, int mode, const void* dy, const void* x, const float* mean, const float* rstd, const float* w,
-                                      void* dx, float* dw, float* db, int N, int H, int W, int cseg, void* stream) {
+                                      void* dx, float* dw, float* db, int N, int H, int W, int cseg, void* ws, void* stream) {
   int64_t M;
   int C;
   if (ln_map_check(mode, N, H, W, cseg, &M, &C)) return -1;
-  return ln_bwd_impl(dtype, dy, x, mean, rstd, w, dx, dw, db, M, C, stream, LnMap{mode, H, W, cseg}, ln_map_vmax(dtype, cseg));
+  return ln_bwd_impl(dtype, dy, x, mean, rstd, w, dx, dw, db, M, C, ws, stream, LnMap{mode, H, W, cseg}, ln_map_vmax(dtype, cseg));
 }

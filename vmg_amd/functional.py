@@ -332,6 +332,22 @@ class _DeferredWgrad:
             self.managed.add(id(p))
         return self.gen
 
+    # the three steps of a node with such parameters: claim() in its forward, into() and done() in its backward
+    def claim(self, ctx, *params):
+        """Decides whether the node's backward adds straight into .grad (ctx.direct) and, if so, counts this use of the parameters."""
+        ctx.direct = self.direct(*params)
+        if ctx.direct:
+            ctx.params, ctx.gen = params, self.note_params(*params)
+
+    def into(self, ctx):
+        """The parameters' .grad buffers for the backward kernel to add into, or None: the gradients are returned through autograd."""
+        return tuple(self.grad_of(p) for p in ctx.params) if ctx.direct else None
+
+    def done(self, ctx):
+        """This use of the parameters is complete, whether the backward kernel ran or the node had nothing to add."""
+        if ctx.direct:
+            self.written(ctx.gen, *ctx.params)
+
     # -- a bias that a Linear / conv manages (its gradient is written by the deferred weight-gradient launch) may ALSO receive gradient from
     #    another node -- the 3-D window attention's q / kv biases, through the zero-padded positions (models/swin_3d.py: the padding is added
     #    before the Linears, so a padded token's q is the bias).  That node adds straight into .grad and the bias counts as complete only
@@ -971,26 +987,41 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     return y
 
 
+def _ln_forward(ctx, x, w, b, eps, mode=None):
+    """Forward of every LayerNorm node: (y, contiguous x).  mode: the space<->depth map ('down' / 'up') of UpdownkeepSampling, or None."""
+    x = x.contiguous()
+    y, mean, rstd = K.layernorm_forward(x, w, b, eps) if mode is None else K.space_depth_ln_forward(x, mode, w, b, eps)
+    ctx.mode = mode
+    ctx.save_for_backward(x, mean, rstd, w)
+    DEFERRED.claim(ctx, w, b)
+    return y, x
+
+
+def _ln_backward(ctx, dys, dskip=None):
+    """Backward of every LayerNorm node: the gradients of (x, w, b).  dys: the list of gradients of the normalised output, summed by the kernel,
+    which also adds dskip, the gradient that reaches x through a skip connection.  dys empty (the normalised branch is unused): dskip alone."""
+    if not dys:
+        DEFERRED.done(ctx)
+        return dskip, None, None
+    x, mean, rstd, w = ctx.saved_tensors
+    if ctx.mode is None:
+        dx, dw, db = K.layernorm_backward(dys, x, mean, rstd, w, into=DEFERRED.into(ctx), add=dskip)
+    else:
+        dx, dw, db = K.space_depth_ln_backward(dys[0], x, ctx.mode, mean, rstd, w, into=DEFERRED.into(ctx))
+    DEFERRED.done(ctx)
+    return (dx, None, None) if ctx.direct else (dx, dw, db)
+
+
 class _LayerNorm(_Fn):
+    """nn.LayerNorm with one consumer: one output, no views, gradients materialised (the cheapest node for the common case)."""
+
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        x = x.contiguous()
-        y, mean, rstd = K.layernorm_forward(x, w, b, eps)
-        ctx.save_for_backward(x, mean, rstd, w)
-        ctx.direct = DEFERRED.direct(w, b)
-        if ctx.direct:
-            ctx.params, ctx.gen = (w, b), DEFERRED.note_params(w, b)
-        return y
+        return _ln_forward(ctx, x, w, b, eps)[0]
 
     @staticmethod
     def backward(ctx, dy):
-        x, mean, rstd, w = ctx.saved_tensors
-        if ctx.direct:
-            dx, _, _ = K.layernorm_backward(dy, x, mean, rstd, w, into=tuple(DEFERRED.grad_of(p) for p in ctx.params))
-            DEFERRED.written(ctx.gen, *ctx.params)
-            return dx, None, None, None
-        dx, dw, db = K.layernorm_backward(dy, x, mean, rstd, w)
-        return dx, dw, db, None
+        return (*_ln_backward(ctx, [dy]), None)
 
 
 class _SpaceDepthLayerNorm(_Fn):
@@ -999,24 +1030,11 @@ class _SpaceDepthLayerNorm(_Fn):
 
     @staticmethod
     def forward(ctx, x, w, b, eps, mode):
-        x = x.contiguous()
-        y, mean, rstd = K.space_depth_ln_forward(x, mode, w, b, eps)
-        ctx.mode = mode
-        ctx.save_for_backward(x, mean, rstd, w)
-        ctx.direct = DEFERRED.direct(w, b)
-        if ctx.direct:
-            ctx.params, ctx.gen = (w, b), DEFERRED.note_params(w, b)
-        return y
+        return _ln_forward(ctx, x, w, b, eps, mode)[0]
 
     @staticmethod
     def backward(ctx, dy):
-        x, mean, rstd, w = ctx.saved_tensors
-        if ctx.direct:
-            dx, _, _ = K.space_depth_ln_backward(dy, x, ctx.mode, mean, rstd, w, into=tuple(DEFERRED.grad_of(p) for p in ctx.params))
-            DEFERRED.written(ctx.gen, *ctx.params)
-            return dx, None, None, None, None
-        dx, dw, db = K.space_depth_ln_backward(dy, x, ctx.mode, mean, rstd, w)
-        return dx, dw, db, None, None
+        return (*_ln_backward(ctx, [dy]), None, None)
 
 
 def space_depth_layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, mode: str) -> torch.Tensor:
@@ -1026,76 +1044,32 @@ def space_depth_layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, ep
     return y.reshape(B, T, *y.shape[1:])
 
 
-class _LayerNormSkip(_Fn):
-    """(LayerNorm(x), x): the second output is x itself, for the skip connection around the normalised branch.  Both gradients meet in
-    THIS node's backward, where the LayerNorm backward kernel adds the skip gradient on its way out (vmg_layernorm_bwd_add) -- autograd
-    would otherwise sum the two with a separate full-size pass per LayerNorm."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, eps):
-        x = x.contiguous()
-        y, mean, rstd = K.layernorm_forward(x, w, b, eps)
-        ctx.save_for_backward(x, mean, rstd, w)
-        ctx.direct = DEFERRED.direct(w, b)
-        if ctx.direct:
-            ctx.params, ctx.gen = (w, b), DEFERRED.note_params(w, b)
-        return y, x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, dy, dskip):
-        x, mean, rstd, w = ctx.saved_tensors
-        into = tuple(DEFERRED.grad_of(p) for p in ctx.params) if ctx.direct else None
-        if dy is None:  # (the normalised branch is unused)
-            return dskip, None, None, None
-        dx, dw, db = K.layernorm_backward(dy, x, mean, rstd, w, into=into, add=dskip)
-        if ctx.direct:
-            DEFERRED.written(ctx.gen, *ctx.params)
-            return dx, None, None, None
-        return dx, dw, db, None
-
-
-def layer_norm_skip(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
-    """(nn.LayerNorm(x), x) with the skip gradient summed inside the LayerNorm backward kernel."""
-    return _LayerNormSkip.apply(x, w, b, eps)
-
-
 class _LayerNormFan(_Fn):
-    """(y_1 .. y_n, x): n handles of the SAME LayerNorm(x) for n consumers, and x for the skip connection.  Autograd hands this node's backward
-    all n output gradients at once; the LayerNorm backward kernel sums them (and the skip gradient) while it reads them
-    (vmg_layernorm_bwd_multi) -- the n - 1 full-size adds autograd would issue for a tensor with n consumers never run."""
+    """(y_1 .. y_n, x): n handles of the SAME LayerNorm(x) for n consumers, and x itself for the skip connection around the normalised branch.
+    Autograd hands this node's backward all n output gradients and the skip gradient at once; the LayerNorm backward kernel sums them while it
+    reads them (vmg_layernorm_bwd) -- neither the n - 1 full-size adds autograd would issue for a tensor with n consumers nor the full-size
+    pass that would add the skip gradient per LayerNorm ever run."""
 
     @staticmethod
     def forward(ctx, x, w, b, eps, n):
-        x = x.contiguous()
-        y, mean, rstd = K.layernorm_forward(x, w, b, eps)
-        ctx.save_for_backward(x, mean, rstd, w)
-        ctx.direct = DEFERRED.direct(w, b)
-        if ctx.direct:
-            ctx.params, ctx.gen = (w, b), DEFERRED.note_params(w, b)
+        y, x = _ln_forward(ctx, x, w, b, eps)
         ctx.set_materialize_grads(False)
-        return (*[y.view_as(y) for _ in range(n)], x.view_as(x))
+        return (*([y] if n == 1 else [y.view_as(y) for _ in range(n)]), x.view_as(x))
 
     @staticmethod
     def backward(ctx, *grads):
-        x, mean, rstd, w = ctx.saved_tensors
-        dys = [g for g in grads[:-1] if g is not None]
-        dskip = grads[-1]
-        if not dys:  # (the normalised branch is unused)
-            if ctx.direct:
-                DEFERRED.written(ctx.gen, *ctx.params)
-            return dskip, None, None, None, None
-        into = tuple(DEFERRED.grad_of(p) for p in ctx.params) if ctx.direct else None
-        dx, dw, db = K.layernorm_backward(dys, x, mean, rstd, w, into=into, add=dskip)
-        if ctx.direct:
-            DEFERRED.written(ctx.gen, *ctx.params)
-            return dx, None, None, None, None
-        return dx, dw, db, None, None
+        return (*_ln_backward(ctx, [g for g in grads[:-1] if g is not None], grads[-1]), None, None)
 
 
 def layer_norm_fan(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float, n: int):
     """([LayerNorm(x)] * n, x): see _LayerNormFan (n <= 5)."""
     out = _LayerNormFan.apply(x, w, b, eps, int(n))
     return list(out[:-1]), out[-1]
+
+
+def layer_norm_skip(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5):
+    """(nn.LayerNorm(x), x) with the skip gradient summed inside the LayerNorm backward kernel: _LayerNormFan with one handle."""
+    return _LayerNormFan.apply(x, w, b, eps, 1)
 
 
 def layer_norm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
@@ -1365,9 +1339,7 @@ class _ChannelAttention(_Fn):
         out = K.tab_elementwise(K.OP_CA_FWD, r, x, coef=g, s=s, G=N)
         ctx.s, ctx.R = s, R
         ctx.save_for_backward(r, g, m, pre, w1, w2)
-        ctx.direct = DEFERRED.direct(w1, b1, w2, b2)
-        if ctx.direct:
-            ctx.params, ctx.gen = (w1, b1, w2, b2), DEFERRED.note_params(w1, b1, w2, b2)
+        DEFERRED.claim(ctx, w1, b1, w2, b2)
         return out
 
     @staticmethod
@@ -1377,11 +1349,10 @@ class _ChannelAttention(_Fn):
         dy = dy.contiguous()
         N = r.shape[0]
         dg = K.group_reduce(dy, N, b=r, mode=1, scale=s)          # d out / d g summed over pixels
-        into = tuple(DEFERRED.grad_of(p) for p in ctx.params) if ctx.direct else None
-        dm, dw1, db1, dw2, db2 = K.se_mlp_backward(dg, g, m, pre, w1.flatten(1), w2.flatten(1), hip.ACT_RELU, 0, 1.0 / R, into=into)  # dm: gradient of the GAP output / R
+        dm, dw1, db1, dw2, db2 = K.se_mlp_backward(dg, g, m, pre, w1.flatten(1), w2.flatten(1), hip.ACT_RELU, 0, 1.0 / R, into=DEFERRED.into(ctx))  # dm: gradient of the GAP output / R
         d_r, d_x = K.tab_elementwise(K.OP_CA_BWD, dy, coef=g, add=dm, s=s, G=N, nout=2)
+        DEFERRED.done(ctx)
         if ctx.direct:
-            DEFERRED.written(ctx.gen, *ctx.params)
             return d_r, d_x, None, None, None, None, None
         return (d_r, d_x, dw1.reshape(w1.shape), db1, dw2.reshape(w2.shape), db2, None)
 
@@ -1494,9 +1465,7 @@ class _ReweightMix(_Fn):
         y = K.tab_elementwise(K.OP_MIX_FWD, h, w, c, coef=a, G=B)
         ctx.R = R
         ctx.save_for_backward(h, w, c, a, m, pre, fc1w, fc2w)
-        ctx.direct = DEFERRED.direct(fc1w, fc1b, fc2w, fc2b)
-        if ctx.direct:
-            ctx.params, ctx.gen = (fc1w, fc1b, fc2w, fc2b), DEFERRED.note_params(fc1w, fc1b, fc2w, fc2b)
+        DEFERRED.claim(ctx, fc1w, fc1b, fc2w, fc2b)
         return y
 
     @staticmethod
@@ -1506,11 +1475,10 @@ class _ReweightMix(_Fn):
         dy = dy.contiguous()
         B, C = h.shape[0], h.shape[-1]
         da = K.group_reduce3(dy, h, w, c, B).reshape(B, 3 * C)  # (B,C,3): d loss / d softmax weights, one pass over dy
-        into = tuple(DEFERRED.grad_of(p) for p in ctx.params) if ctx.direct else None
-        dm, dw1, db1, dw2, db2 = K.se_mlp_backward(da, a, m, pre, fc1w, fc2w, hip.ACT_GELU, 1, 1.0 / R, into=into)   # softmax, Linear, GELU, Linear backward
+        dm, dw1, db1, dw2, db2 = K.se_mlp_backward(da, a, m, pre, fc1w, fc2w, hip.ACT_GELU, 1, 1.0 / R, into=DEFERRED.into(ctx))   # softmax, Linear, GELU, Linear backward
         dh, dw, dc = K.tab_elementwise(K.OP_MIX_BWD, dy, coef=a, add=dm, G=B, nout=3)
+        DEFERRED.done(ctx)
         if ctx.direct:
-            DEFERRED.written(ctx.gen, *ctx.params)
             return dh, dw, dc, None, None, None, None
         return dh, dw, dc, dw1, db1, dw2, db2
 

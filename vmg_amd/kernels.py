@@ -484,43 +484,49 @@ def _grad_pair(C: int, device, into):
     return dw, db
 
 
-def layernorm_backward(dy, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, w: torch.Tensor, into=None, add=None):
-    """into = (dw, db): the kernel's atomic sums are ADDED to these buffers (param.grad) instead of to fresh zero tensors.
-    add: a gradient of x's shape that is summed into dx by the kernel (the skip-connection gradient).
-    dy: one gradient, or a list of up to five gradients of the LayerNorm output that the kernel sums on the way in."""
+def layernorm_backward(dys, x: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, w: torch.Tensor, into=None, add=None):
+    """dys: one gradient, or a list of up to five gradients of the LayerNorm output that the kernel sums on the way in.
+    into = (dw, db): the kernel's atomic sums are ADDED to these buffers (param.grad) instead of to fresh zero tensors.
+    add: a gradient of x's shape that is summed into dx by the kernel (the skip-connection gradient)."""
+    dys = [d.contiguous() for d in dys] if isinstance(dys, (list, tuple)) else [dys.contiguous()]
+    hip.require_cuda(x, mean, rstd, w, add, *dys)
+    if not 1 <= len(dys) <= 5:
+        raise HipError("layernorm_backward: 1..5 output gradients expected")
+    for t in dys if add is None else (*dys, add):
+        if t.shape != x.shape or t.dtype != x.dtype:
+            raise HipError("layernorm_backward: the output gradients and add must have x's shape and dtype")
+    if add is not None:
+        add = add.contiguous()
     C = x.shape[-1]
-    M = x.numel() // C
-    if isinstance(dy, (list, tuple)):
-        dys = [d.contiguous() for d in dy]
-        hip.require_cuda(x, mean, rstd, w, add, *dys)
-        if not 1 <= len(dys) <= 5 or any(d.shape != x.shape or d.dtype != x.dtype for d in dys):
-            raise HipError("layernorm_backward: 1..5 output gradients of x's shape and dtype expected")
-        dx = torch.empty_like(x)
-        dw, db = _grad_pair(C, x.device, into)
-        if add is not None:
-            if add.shape != x.shape or add.dtype != x.dtype:
-                raise HipError("layernorm_backward: add must have x's shape and dtype")
-            add = add.contiguous()
-        hip.check(hip.lib().vmg_layernorm_bwd_multi(hip.dtype_code(x.dtype), len(dys), _ptrs(dys), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(),
-                                                    add.data_ptr() if add is not None else None, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), M, C,
-                                                    hip.stream_ptr()), "vmg_layernorm_bwd_multi")
-        return dx, dw, db
-    hip.require_cuda(dy, x, mean, rstd, w, add)
-    dy = dy.contiguous()
     dx = torch.empty_like(x)
     dw, db = _grad_pair(C, x.device, into)
-    if add is not None:
-        if add.shape != x.shape or add.dtype != x.dtype:
-            raise HipError("layernorm_backward: add must have x's shape and dtype")
-        add = add.contiguous()
-        hip.check(hip.lib().vmg_layernorm_bwd_add(hip.dtype_code(x.dtype), dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(),
-                                                  add.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), M, C, hip.stream_ptr()),
-                  "vmg_layernorm_bwd_add")
-        return dx, dw, db
-    hip.check(hip.lib().vmg_layernorm_bwd(hip.dtype_code(x.dtype), dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                          w.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(), M, C, hip.stream_ptr()),
-              "vmg_layernorm_bwd")
+    ws = _layernorm_workspace(x.device)
+    hip.check(hip.lib().vmg_layernorm_bwd(hip.dtype_code(x.dtype), len(dys), _ptrs(dys), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(),
+                                          add.data_ptr() if add is not None else None, dx.data_ptr(), dw.data_ptr(), db.data_ptr(), x.numel() // C, C,
+                                          ws.data_ptr() if ws is not None else None, hip.stream_ptr()), "vmg_layernorm_bwd")
     return dx, dw, db
+
+
+_WS = {}
+
+
+def _workspace(size_entry: str, device, zero: bool = False) -> torch.Tensor:
+    """A kernel family's scratch buffer of lib.<size_entry>() bytes: allocated once per device on first use and kept (the calls that share
+    one are stream-ordered on the device's compute stream)."""
+    ws = _WS.get((size_entry, device))
+    if ws is None:
+        nbytes = int(getattr(hip.lib(), size_entry)())
+        ws = _WS[size_entry, device] = (torch.zeros if zero else torch.empty)(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _layernorm_workspace(device) -> Optional[torch.Tensor]:
+    """The zeroed workspace of the LayerNorm backward (the kernel leaves it zero), or None -- the kernel's plain-atomic tail -- while it does
+    not exist and the stream is capturing: it must not come from a graph's private pool, and a captured step's warm-up creates it anyway."""
+    ws = _WS.get(("vmg_layernorm_bwd_ws_bytes", device))
+    if ws is None and not torch.cuda.is_current_stream_capturing():
+        ws = _workspace("vmg_layernorm_bwd_ws_bytes", device, zero=True)
+    return ws
 
 
 MORPH_FUSED_CP = (144, 112, 64, 32, 16)
@@ -763,8 +769,10 @@ def space_depth_ln_backward(dy: torch.Tensor, x: torch.Tensor, mode: str, mean: 
     dy = dy.contiguous()
     dx = torch.empty_like(x)
     dw, db = _grad_pair(C, x.device, into)
+    ws = _layernorm_workspace(x.device)
     hip.check(hip.lib().vmg_space_depth_ln_bwd(hip.dtype_code(x.dtype), m, dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), w.data_ptr(),
-                                               dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, cseg, hip.stream_ptr()), "vmg_space_depth_ln_bwd")
+                                               dx.data_ptr(), dw.data_ptr(), db.data_ptr(), N, H, W, cseg, ws.data_ptr() if ws is not None else None,
+                                               hip.stream_ptr()), "vmg_space_depth_ln_bwd")
     return dx, dw, db
 
 
@@ -790,7 +798,7 @@ def conv_wgrad_batched(xs: Sequence[torch.Tensor], dys: Sequence[torch.Tensor], 
         raise HipError(f"gradient tensor {tuple(dW.shape)} does not match conv (ks={ks}, Cout={Cout}+{o0}, Cin={Cin}+{i0})")
     code = hip.dtype_code(x0.dtype)
     l = hip.lib()
-    ws = _wgrad_workspace(dW.device)
+    ws = _workspace("vmg_conv_wgrad_ws_bytes", dW.device)
     for s in range(0, len(xs), 16):
         n = min(16, len(xs) - s)
         xa = (ctypes.c_void_p * n)(*[t.data_ptr() for t in xs[s:s + n]])
@@ -829,7 +837,7 @@ def linear_wgrad2_multi(probs, M: int):
     if dW0.shape[0] != Cout or Cin != I_total or dW0.numel() != Cout * Cin:
         raise HipError("linear_wgrad2_multi: gradient tensor does not match the layer")
     l = hip.lib()
-    ws = _wgrad_workspace(dW0.device)
+    ws = _workspace("vmg_conv_wgrad_ws_bytes", dW0.device)
     for s in range(0, len(probs), 8):
         grp = probs[s:s + 8]
         n = len(grp)
@@ -863,7 +871,7 @@ def conv_wgrad3_multi(probs, N: int, H: int, W: int):
     if dW0.shape[0] != Cout or dW0.dim() != 4 or dW0.shape[2] != 3 or Cin > I_total:
         raise HipError("conv_wgrad3_multi: gradient tensor does not match the convolution")
     l = hip.lib()
-    ws = _wgrad_workspace(dW0.device)
+    ws = _workspace("vmg_conv_wgrad_ws_bytes", dW0.device)
     for s in range(0, len(probs), 8):
         grp = probs[s:s + 8]
         n = len(grp)
@@ -874,19 +882,6 @@ def conv_wgrad3_multi(probs, N: int, H: int, W: int):
         sa = (ctypes.c_float * n)(*[float(g[4]) for g in grp])
         hip.check(l.vmg_conv_wgrad3_multi(n, npairs, xa, da, N, H, W, xps, Cin, dps, Cout, wa, I_total, 0, 0, ba, sa, ws.data_ptr(), ws.numel(),
                                           hip.stream_ptr()), "vmg_conv_wgrad3_multi")
-
-
-_WGRAD_WS = {}
-
-
-def _wgrad_workspace(device) -> torch.Tensor:
-    """Slab workspace of the large-tile weight-gradient kernel: allocated once per device, reused (calls are stream-ordered)."""
-    key = str(device)
-    ws = _WGRAD_WS.get(key)
-    if ws is None:
-        ws = torch.empty(int(hip.lib().vmg_conv_wgrad_ws_bytes()), dtype=torch.uint8, device=device)
-        _WGRAD_WS[key] = ws
-    return ws
 
 
 def _ptrs(ts):
@@ -1009,24 +1004,11 @@ def group_reduce(a: torch.Tensor, G: int, b: Optional[torch.Tensor] = None, c3: 
     if rows % G or not a.is_contiguous() or any(t is not None and (t.shape != a.shape or t.dtype != a.dtype or not t.is_contiguous()) for t in (b, c3)):
         raise HipError("group_reduce: contiguous tensors of one shape / dtype covering G groups expected")
     out = torch.empty((G, C), dtype=torch.float32, device=a.device)
-    ws = _group_reduce_workspace(a.device)
+    ws = _workspace("vmg_group_reduce_ws_bytes", a.device)
     hip.check(hip.lib().vmg_group_reduce(hip.dtype_code(a.dtype), a.data_ptr(), b.data_ptr() if b is not None else None,
                                          c3.data_ptr() if c3 is not None else None, out.data_ptr(), G, rows // G, C, mode, scale,
                                          ws.data_ptr(), ws.numel(), hip.stream_ptr()), "vmg_group_reduce")
     return out
-
-
-_GR_WS = {}
-
-
-def _group_reduce_workspace(device) -> torch.Tensor:
-    """Block-partials workspace of the pooled sums: allocated once per device, reused (the calls are stream-ordered: a call's second launch
-    has read the partials before the next call's first launch writes them)."""
-    key = str(device)
-    ws = _GR_WS.get(key)
-    if ws is None:
-        ws = _GR_WS[key] = torch.empty(int(hip.lib().vmg_group_reduce_ws_bytes()), dtype=torch.uint8, device=device)
-    return ws
 
 
 def group_reduce3(a: torch.Tensor, b0: torch.Tensor, b1: torch.Tensor, b2: torch.Tensor, G: int, scale: float = 1.0) -> torch.Tensor:
@@ -1037,7 +1019,7 @@ def group_reduce3(a: torch.Tensor, b0: torch.Tensor, b1: torch.Tensor, b2: torch
     if rows % G or any(t.shape != a.shape or t.dtype != a.dtype or not t.is_contiguous() for t in (a, b0, b1, b2)):
         raise HipError("group_reduce3: contiguous tensors of one shape / dtype covering G groups expected")
     out = torch.empty((G, C, 3), dtype=torch.float32, device=a.device)
-    ws = _group_reduce_workspace(a.device)
+    ws = _workspace("vmg_group_reduce_ws_bytes", a.device)
     hip.check(hip.lib().vmg_group_reduce3(hip.dtype_code(a.dtype), a.data_ptr(), b0.data_ptr(), b1.data_ptr(), b2.data_ptr(), out.data_ptr(), G,
                                           rows // G, C, scale, ws.data_ptr(), ws.numel(), hip.stream_ptr()), "vmg_group_reduce3")
     return out
