@@ -469,6 +469,17 @@ int vmg_tile_accumulate(int dtype, const void* patch, float* E, float* Wt, int64
                         int top, int bottom, int left, int right, void* stream);
 int vmg_tile_finalize(const float* E, const float* Wt, float* out_f32, unsigned char* out_u8, int64_t n, void* stream);
 
+/* ---- MorphFC retention decay, n calls at once (reference: Enhanced_MorphFCs_decay.forward, models/function.py:766-768, 779-781: every
+ * forward call multiplies the mlp_h / mlp_w weights by their Gamma buffer in place, in eval mode too -- call k of a freshly loaded model
+ * sees W * Gamma^k) --------------------------------------------------------------------------------------------------------------
+ * w, gamma, numel: HOST arrays of `count` (>= 1, any length: lists beyond the kernel's argument table take several launches) device
+ * pointers / element counts; w[i] and gamma[i] are dense fp32 runs of numel[i] elements.  w[i] <- w[i] * gamma[i] * ... * gamma[i],
+ * n (>= 1) factors: each element is loaded once, multiplied n times in a register -- one ROUNDED fp32 multiply after the other, never a
+ * power -- and stored once, so the result has the bits of n separate in-place multiplies (denormals kept).  16-byte vectors where a
+ * tensor and its Gamma reach a 16-byte boundary at the same element, single elements in front of / behind that and everywhere else:
+ * no alignment or size precondition beyond 4-byte aligned floats. */
+int vmg_decay_weights(float* const* w, const float* const* gamma, const int64_t* numel, int count, int n, void* stream);
+
 /* ---- AdamW over a flat fp32 segment (reference: torch.optim.AdamW as set up in tools/Trainer.py:86-105) -----------------
  * p, g, m, v: parameter, gradient, exp_avg, exp_avg_sq (n floats each, 16-byte aligned).  hyper (DEVICE memory, 4 floats):
  * lr, weight_decay, 1 - beta1^t, sqrt(1 - beta2^t).  torch's update order and formula, no amsgrad. */

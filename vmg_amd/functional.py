@@ -96,6 +96,7 @@ class _PackCache:
         self.stamp = 0          # bumped when the set of plan-eligible packs changes (new pack, a key turned volatile, cache cleared)
         self.stable = _PlanState()  # repack_all: every plan-eligible pack that is not volatile
         self.vol = _PlanState()     # decay_weights_and_repack: the volatile packs of the decayed weights
+        self.decay = None           # decay_weights_and_repack: ((ids of the weights, ids of the Gammas), their K.DecayList)
 
     def get(self, key, weight: torch.Tensor, build, planned: bool = True):
         """The cached image under `key`, current for `weight`; on a miss build(key, weight, buf) makes it (buf: the stale image's buffer of
@@ -126,6 +127,7 @@ class _PackCache:
         self.ents.clear()
         self.q8.clear()
         self.volatile.clear()
+        self.decay = None
         self.stamp += 1
 
     def bump_epoch(self):
@@ -160,13 +162,21 @@ class _PackCache:
         rebuilt only when the cache's membership has changed -- this runs at the very end of a step, with the GPU idle behind it."""
         self._run_plan(self.stable, None, lambda key, ent: key not in self.volatile and _from_param(ent))
 
-    def decay_weights_and_repack(self, weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor]):
-        """W <- W * Gamma for all the given weights in ONE launch and their cached packs rebuilt in ONE more (the MorphFC retention decay of
-        every token mixer of a model, reference models/function.py:766-768 / 779-781, applied at the top of the model's forward instead of
-        module by module: 24 small multiplies and 48 pack launches per step otherwise).  Packs that are not cached yet are built on demand."""
-        with torch.no_grad():
-            torch._foreach_mul_(list(weights), list(gammas))
-        wkey = tuple(id(w) for w in weights)
+    def decay_weights_and_repack(self, weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor], n: int = 1):
+        """W <- W * Gamma (n times: the decay of n forward calls, each multiply rounded like a call's own) for all the given weights in ONE
+        launch (vmg_decay_weights) and their cached packs rebuilt in ONE more (the MorphFC retention decay of every token mixer of a model,
+        reference models/function.py:766-768 / 779-781, applied at the top of the model's forward instead of module by module: 24 small
+        multiplies and 48 pack launches per step otherwise).  Packs that are not cached yet are built on demand."""
+        wkey = tuple(map(id, weights))
+        if weights[0].is_cuda:
+            dkey = (wkey, tuple(map(id, gammas)))
+            if self.decay is None or self.decay[0] != dkey:
+                self.decay = (dkey, K.DecayList(weights, gammas))  # (holds the tensors: their ids stay theirs)
+            self.decay[1].run(n)
+        else:  # (host tensors: the cache's bookkeeping driven without a device, tests/test_host_logic.py -- no kernel can touch them)
+            with torch.no_grad():
+                for _ in range(int(n)):
+                    torch._foreach_mul_(list(weights), list(gammas))
         ids = set(wkey)
         self._run_plan(self.vol, wkey, lambda key, ent: key in self.volatile and id(ent[2]) in ids and _from_param(ent), reset_sig=True)
 

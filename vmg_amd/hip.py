@@ -165,6 +165,7 @@ SIGNATURES = {
     "vmg_tile_accumulate": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_void_p]),
     "vmg_tile_finalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vmg_decay_weights": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int64), c_int, c_int, c_void_p]),
     "vmg_conv_debug_stamps": (c_int, [c_void_p]),
     "vmg_create": (c_void_p, [c_int]),
     "vmg_destroy": (c_int, [c_void_p]),

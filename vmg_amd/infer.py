@@ -5,11 +5,16 @@ half-overlap conventions (`-overlap//2:` drops ceil(overlap/2) trailing rows/fra
 ones, counted in OUTPUT pixels with the LOW-resolution overlap, exactly as the reference slices them).  The canvases stay
 in HBM; each tile is folded in by one HIP kernel (vmg_tile_accumulate) and the division / clamp / uint8 rounding is one
 more (vmg_tile_finalize).  There is no CPU path: tensors must live on the GPU.
+
+The three window functions are plan_calls -> run_calls -> blend: the list of network calls in visiting order (host logic), a
+contiguous run of them executed at the right call index (VMG.set_forward_calls), and the fold of all tile outputs in plan
+order.  test_clips_sharded spreads the calls of one sequence over the ranks of a torch.distributed group and folds on rank 0:
+the same bits as one process walking all calls.
 """
 from __future__ import annotations
 
 import math
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -31,6 +36,17 @@ class GraphedModel:
     def _mixer_weights(self):
         return [p for n, p in self.model.named_parameters() if n.endswith("mlp_h.0.weight") or n.endswith("mlp_w.0.weight")]
 
+    # the model's call index (VMG.forward_calls): the warm-up calls do not count, every replay does
+    @property
+    def forward_calls(self) -> int:
+        return self.model.forward_calls
+
+    def advance_calls(self, n: int) -> None:
+        self.model.advance_calls(n)
+
+    def set_forward_calls(self, k: int) -> None:
+        self.model.set_forward_calls(k)
+
     @torch.no_grad()
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         hip.require_cuda(x)
@@ -51,6 +67,7 @@ class GraphedModel:
             static_in = x.clone()
             ws = self._mixer_weights()
             saved = [w.detach().clone() for w in ws]
+            calls0 = self.model._forward_calls
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -66,10 +83,12 @@ class GraphedModel:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 static_out = self.model(static_in)
+            self.model._forward_calls = calls0  # (the warm-up calls were undone above, and capturing runs nothing)
             ent = self.graphs[key] = (g, static_in, static_out)
         g, static_in, static_out = ent
         static_in.copy_(x)
         g.replay()
+        self.model._forward_calls += 1  # (the decay is part of the graph)
         return static_out.clone()
 
 
@@ -104,47 +123,219 @@ def _finalize(E: torch.Tensor, Wt: torch.Tensor, want_u8: bool = False):
     return u8 if want_u8 else out
 
 
+class PlannedCall(NamedTuple):
+    """One network call of a sequence: `index` = its 1-based position in the visiting order, `t` = first frame of its temporal window,
+    `origin` = (h, w) of its spatial tile in LR pixels, None for whole frames."""
+    index: int
+    t: int
+    origin: Optional[Tuple[int, int]]
+
+
+class CallPlan:
+    """The ordered network calls of one sequence (tools/Tester.py:107-175: outer loop temporal windows, inner loops tile rows then
+    columns) with the window arithmetic the fold needs.  Behaves as the list of its PlannedCall entries."""
+
+    def __init__(self, T: int, H: int, W: int, num_frames: int, overlap_frames: int, test_spatial: Optional[Sequence[int]] = None,
+                 overlap_spatial: Optional[int] = None):
+        self.T, self.H, self.W, self.num_frames, self.overlap_frames = int(T), int(H), int(W), int(num_frames), int(overlap_frames)
+        self.ts = tile_starts(self.T, self.num_frames, self.overlap_frames)
+        self.overlap_spatial = None if overlap_spatial is None else int(overlap_spatial)
+        if self.overlap_spatial is None:
+            self.th = self.tw = self.hs = self.ws = None
+            origins = [None]
+        else:
+            self.th, self.tw = (int(v) for v in test_spatial)
+            self.hs, self.ws = tile_starts(self.H, self.th, self.overlap_spatial), tile_starts(self.W, self.tw, self.overlap_spatial)
+            origins = [(h, w) for h in self.hs for w in self.ws]
+        self.per_window = len(origins)
+        self.calls = [PlannedCall(i * self.per_window + j + 1, t, o) for i, t in enumerate(self.ts) for j, o in enumerate(origins)]
+
+    def __len__(self):
+        return len(self.calls)
+
+    def __iter__(self):
+        return iter(self.calls)
+
+    def __getitem__(self, i):
+        return self.calls[i]
+
+    def crop(self, inputs: torch.Tensor, call: PlannedCall) -> torch.Tensor:
+        """The call's input: its temporal window of (B, T, C, H, W), cut to its spatial tile."""
+        clip = inputs[:, call.t:call.t + self.num_frames]
+        if call.origin is None:
+            return clip
+        h, w = call.origin
+        return clip[..., h:h + self.th, w:w + self.tw]
+
+    def margins(self, call: PlannedCall, out: torch.Tensor):
+        """(top, bottom, left, right) output rows / columns of the tile that its neighbours cover instead."""
+        ov, hs, ws = self.overlap_spatial, self.hs, self.ws
+        h, w = call.origin
+        lead = ov // 2  # `:overlap//2` of the reference
+        # `-overlap//2:` drops the last ceil(overlap/2) rows -- and, faithfully, EVERY row when overlap == 0 (the slice is
+        # then `0:`; the reference yields 0/0 = NaN there: tiles without overlap are not a supported setting of it)
+        trail_h = -(-ov // 2) if ov > 0 else out.shape[-2]
+        trail_w = -(-ov // 2) if ov > 0 else out.shape[-1]
+        return (lead if h > hs[0] else 0, trail_h if h < hs[-1] else 0, lead if w > ws[0] else 0, trail_w if w < ws[-1] else 0)
+
+
+def plan_calls(T: int, H: int, W: int, num_frames: int, overlap_frames: int, test_spatial: Optional[Sequence[int]] = None,
+               overlap_spatial: Optional[int] = None) -> CallPlan:
+    """The network calls test_clips makes on a (B, T, C, H, W) sequence, in its visiting order.  Host logic only."""
+    return CallPlan(T, H, W, num_frames, overlap_frames, test_spatial, overlap_spatial)
+
+
+def shard_ranges(n_calls: int, world: int) -> List[range]:
+    """1-based plan positions of each of `world` ranks: contiguous runs in rank order, lengths within one call of each other (the first
+    n_calls % world ranks take the longer ones; a rank beyond the plan's length gets an empty range)."""
+    if n_calls < 0 or world < 1:
+        raise ValueError("shard_ranges: n_calls >= 0 and world >= 1 expected")
+    q, r = divmod(n_calls, world)
+    out, lo = [], 1
+    for k in range(world):
+        n = q + (1 if k < r else 0)
+        out.append(range(lo, lo + n))
+        lo += n
+    return out
+
+
+def _has_counter(model) -> bool:
+    return hasattr(model, "forward_calls") and hasattr(model, "set_forward_calls")
+
+
+def _entries(plan: CallPlan, calls) -> List[PlannedCall]:
+    ents = [c if isinstance(c, PlannedCall) else plan[int(c) - 1] for c in calls]
+    for a, b in zip(ents, ents[1:]):
+        if b.index != a.index + 1:
+            raise ValueError("run_calls: the calls must be a contiguous run of the plan, in plan order")
+    for e in ents:
+        if not 1 <= e.index <= len(plan) or plan[e.index - 1] != e:
+            raise ValueError(f"run_calls: call {e.index} is not an entry of this plan")
+    return ents
+
+
+@torch.no_grad()
+def run_calls(model: Callable, inputs: torch.Tensor, plan: CallPlan, calls, first_call: Optional[int] = None) -> List[torch.Tensor]:
+    """Runs a contiguous sub-range of the plan -- `calls`: 1-based positions (e.g. range(3, 5)) or plan entries (plan[2:4]) -- and returns
+    the tile outputs in that order.  The network is stateful (every call decays the mixer weights): with first_call = k the model is first
+    moved to k - 1 applied calls (model.set_forward_calls), so that the first call made here is call k since the checkpoint was loaded;
+    without it a model that counts its calls must stand exactly in front of the first position given.  Plain callables without a
+    counter are called as they are."""
+    hip.require_cuda(inputs)
+    ents = _entries(plan, calls)
+    if tuple(inputs.shape[1:2] + inputs.shape[3:]) != (plan.T, plan.H, plan.W):
+        raise ValueError(f"run_calls: the plan is for (T, H, W) = {(plan.T, plan.H, plan.W)}, the inputs are {tuple(inputs.shape)}")
+    if not ents:
+        return []
+    if first_call is not None:
+        if not _has_counter(model):
+            raise ValueError("run_calls: first_call needs a model that counts its calls (forward_calls / set_forward_calls)")
+        model.set_forward_calls(int(first_call) - 1)
+    elif _has_counter(model) and model.forward_calls + 1 != ents[0].index:
+        raise ValueError(f"run_calls: the model has made {model.forward_calls} calls, so its next one is not call {ents[0].index} of the plan; "
+                         "pass first_call to move it there")
+    return [model(plan.crop(inputs, c)) for c in ents]
+
+
+def _blend_window(plan: CallPlan, calls: Sequence[PlannedCall], outs: Sequence[torch.Tensor], dtype: torch.dtype, scale: int) -> torch.Tensor:
+    """One temporal window from its calls' outputs (tools/Tester.py:107-141): the sole whole-frame output, or the spatial tiles folded in
+    plan order."""
+    if plan.overlap_spatial is None:
+        return outs[0]
+    B, tf, C = outs[0].shape[:3]
+    E = torch.zeros(B, tf, C, plan.H * scale, plan.W * scale, dtype=torch.float32, device=outs[0].device)
+    Wt = torch.zeros_like(E)
+    for c, out in zip(calls, outs):
+        _accumulate(out, E, Wt, c.origin[0] * scale, c.origin[1] * scale, plan.margins(c, out))
+    return _finalize(E, Wt).to(dtype)
+
+
+@torch.no_grad()
+def blend(plan: CallPlan, outputs: Sequence[torch.Tensor], dtype: Optional[torch.dtype] = None, scale: int = 4) -> torch.Tensor:
+    """Folds the tile outputs of ALL calls of the plan, given in plan order, into the (B, T, C, H * scale, W * scale) frames: spatial
+    tiles by vmg_tile_accumulate / vmg_tile_finalize per temporal window, the windows by slice adds (tools/Tester.py:143-175).  fp32 sums
+    depend on their order, so the fold always runs in plan order on one device: who computed which tile does not show in the result."""
+    if len(outputs) != len(plan):
+        raise ValueError(f"blend: the plan has {len(plan)} calls, {len(outputs)} outputs were given")
+    hip.require_cuda(*outputs)
+    dtype = outputs[0].dtype if dtype is None else dtype
+    B, _, C = outputs[0].shape[:3]
+    E = torch.zeros(B, plan.T, C, plan.H * scale, plan.W * scale, dtype=torch.float32, device=outputs[0].device)
+    N = torch.zeros(B, plan.T, 1, 1, 1, dtype=torch.float32, device=outputs[0].device)
+    ts, nf, of, pw = plan.ts, plan.num_frames, plan.overlap_frames, plan.per_window
+    lead, trail = of // 2, -(-of // 2)
+    for i, t in enumerate(ts):
+        out = _blend_window(plan, plan[i * pw:(i + 1) * pw], outputs[i * pw:(i + 1) * pw], dtype, scale)
+        lo = lead if (of > 0 and t > ts[0]) else 0
+        hi = nf - (trail if (of > 0 and t < ts[-1]) else 0)
+        # frames are whole planes: a slice add is already one pass
+        E[:, t + lo:t + hi].add_(out[:, lo:hi].float())
+        N[:, t + lo:t + hi].add_(1.0)
+    return E.div_(N).to(dtype)
+
+
+def _run_all(model: Callable, inputs: torch.Tensor, plan: CallPlan) -> List[torch.Tensor]:
+    """Every call of the plan, continuing from wherever the model's call count stands (the reference keeps decaying across sequences)."""
+    return run_calls(model, inputs, plan, plan.calls, first_call=model.forward_calls + 1 if _has_counter(model) else None)
+
+
 @torch.no_grad()
 def test_image(model: Callable, inputs: torch.Tensor, test_spatial: Sequence[int], overlap: int, scale: int = 4) -> torch.Tensor:
     """tools/Tester.py:107-141: spatial tiles of `test_spatial` with `overlap` LR pixels between neighbours."""
     hip.require_cuda(inputs)
     B, T, C, H, W = inputs.shape
-    th, tw = test_spatial
-    hs, ws = tile_starts(H, th, overlap), tile_starts(W, tw, overlap)
-    E = torch.zeros(B, T, C, H * scale, W * scale, dtype=torch.float32, device=inputs.device)
-    Wt = torch.zeros_like(E)
-    lead = overlap // 2  # `:overlap//2` of the reference
-    for h in hs:
-        for w in ws:
-            out = model(inputs[..., h:h + th, w:w + tw])
-            # `-overlap//2:` drops the last ceil(overlap/2) rows -- and, faithfully, EVERY row when overlap == 0 (the slice is
-            # then `0:`; the reference yields 0/0 = NaN there: tiles without overlap are not a supported setting of it)
-            trail_h = -(-overlap // 2) if overlap > 0 else out.shape[-2]
-            trail_w = -(-overlap // 2) if overlap > 0 else out.shape[-1]
-            margins = (lead if h > hs[0] else 0, trail_h if h < hs[-1] else 0, lead if w > ws[0] else 0, trail_w if w < ws[-1] else 0)
-            _accumulate(out, E, Wt, h * scale, w * scale, margins)
-    return _finalize(E, Wt).to(inputs.dtype)
+    plan = CallPlan(T, H, W, max(T, 1), 0, test_spatial, overlap)  # one temporal window: all frames
+    return _blend_window(plan, plan.calls, _run_all(model, inputs, plan), inputs.dtype, scale)
 
 
 @torch.no_grad()
 def test_clips(model: Callable, inputs: torch.Tensor, num_frames: int, overlap_frames: int, test_spatial: Optional[Sequence[int]] = None,
                overlap_spatial: Optional[int] = None, scale: int = 4) -> torch.Tensor:
-    """tools/Tester.py:143-175: temporal windows of `num_frames` with `overlap_frames` shared frames."""
+    """tools/Tester.py:143-175: temporal windows of `num_frames` with `overlap_frames` shared frames: plan -> run all -> blend."""
     hip.require_cuda(inputs)
     B, T, C, H, W = inputs.shape
-    E = torch.zeros(B, T, C, H * scale, W * scale, dtype=torch.float32, device=inputs.device)
-    N = torch.zeros(B, T, 1, 1, 1, dtype=torch.float32, device=inputs.device)
-    ts = tile_starts(T, num_frames, overlap_frames)
-    lead, trail = overlap_frames // 2, -(-overlap_frames // 2)
-    for t in ts:
-        clip = inputs[:, t:t + num_frames]
-        out = model(clip) if overlap_spatial is None else test_image(model, clip, test_spatial, overlap_spatial, scale)
-        lo = lead if (overlap_frames > 0 and t > ts[0]) else 0
-        hi = num_frames - (trail if (overlap_frames > 0 and t < ts[-1]) else 0)
-        # frames are whole planes: a slice add is already one pass
-        E[:, t + lo:t + hi].add_(out[:, lo:hi].float())
-        N[:, t + lo:t + hi].add_(1.0)
-    return E.div_(N).to(inputs.dtype)
+    plan = plan_calls(T, H, W, num_frames, overlap_frames, test_spatial, overlap_spatial)
+    return blend(plan, _run_all(model, inputs, plan), inputs.dtype, scale)
+
+
+@torch.no_grad()
+def test_clips_sharded(model: Callable, inputs: torch.Tensor, num_frames: int, overlap_frames: int, test_spatial: Optional[Sequence[int]] = None,
+                       overlap_spatial: Optional[int] = None, scale: int = 4, group=None) -> Optional[torch.Tensor]:
+    """test_clips with the network calls of ONE sequence spread over the ranks of an initialised torch.distributed group: rank r runs a
+    contiguous run of the plan (shard_ranges) starting at the right call index, the tile outputs travel to rank 0 in the model's output
+    dtype, rank 0 folds them in plan order -- the bits of the single-process result -- and returns the frames; the other ranks return
+    None.  Every replica must hold the same weights at the same call count on entry; all leave with the count of a single process that
+    ran the whole sequence, so the next sequence continues the same way.  World size 1 or no group: test_clips."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return test_clips(model, inputs, num_frames, overlap_frames, test_spatial, overlap_spatial, scale)
+    hip.require_cuda(inputs)
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    B, T, C, H, W = inputs.shape
+    plan = plan_calls(T, H, W, num_frames, overlap_frames, test_spatial, overlap_spatial)
+    ranges = shard_ranges(len(plan), world)
+    mine = ranges[rank]
+    counted = _has_counter(model)
+    base = model.forward_calls if counted else 0
+    outs = run_calls(model, inputs, plan, mine, first_call=base + mine.start if counted and len(mine) else None)
+    if counted:
+        model.set_forward_calls(base + len(plan))
+    src_of = (lambda r: dist.get_global_rank(group, r)) if group is not None else (lambda r: r)
+    # every tile of a plan has one shape; rank 0 (never without a call) tells the others what a tile looks like
+    meta = [(tuple(outs[0].shape), outs[0].dtype) if rank == 0 else None]
+    dist.broadcast_object_list(meta, src=src_of(0), group=group)
+    shape, odtype = meta[0]
+    tiles: List[torch.Tensor] = []
+    for r in range(world):
+        if not len(ranges[r]):
+            continue
+        # one broadcast per shard: the collective both gloo and RCCL carry for device tensors (no gather / send there on gloo).  The
+        # tiles move as the BYTES of the model's output dtype: gloo knows neither bf16 nor int16, every backend knows uint8
+        buf = torch.stack([o.contiguous() for o in outs]) if r == rank else torch.empty((len(ranges[r]), *shape), dtype=odtype, device=inputs.device)
+        dist.broadcast(buf.view(torch.uint8), src=src_of(r), group=group)
+        if rank == 0:
+            tiles.extend(buf.unbind(0))
+    return blend(plan, tiles, inputs.dtype, scale) if rank == 0 else None
 
 
 def _psnr01(a: torch.Tensor, b: torch.Tensor) -> float:

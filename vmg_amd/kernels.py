@@ -382,6 +382,43 @@ def sum_n(ts: Sequence[torch.Tensor]) -> torch.Tensor:
     return out
 
 
+class DecayList:
+    """A list of (weight, Gamma) pairs for vmg_decay_weights with its pointer tables kept between calls: the per-call decay runs at the top of
+    every forward, and 48 tensors' worth of argument checks and ctypes conversions there is host time of a host-bound step.  The tables are
+    rebuilt (and the tensors checked again) whenever a data pointer has moved (module.to(), an optimizer that re-lays its parameters)."""
+
+    def __init__(self, weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor]):
+        if not weights or len(weights) != len(gammas):
+            raise HipError("decay_weights: two non-empty lists of equal length expected")
+        self.weights, self.tensors, self.ptrs, self.args = list(weights), list(weights) + list(gammas), None, None
+
+    def _tables(self, ptrs):
+        cnt = len(self.weights)
+        hip.require_cuda(*self.tensors)
+        for w, g in zip(self.weights, self.tensors[cnt:]):
+            if w.dtype != torch.float32 or g.dtype != torch.float32 or w.numel() != g.numel() or w.numel() == 0 or not w.is_contiguous() or not g.is_contiguous():
+                raise HipError("decay_weights: dense fp32 weights and Gammas of the same non-zero element counts expected")
+        self.args = ((ctypes.c_void_p * cnt)(*ptrs[:cnt]), (ctypes.c_void_p * cnt)(*ptrs[cnt:]), (ctypes.c_int64 * cnt)(*[w.numel() for w in self.weights]), cnt)
+        self.ptrs = ptrs
+
+    def run(self, n: int = 1) -> None:
+        n = int(n)
+        if n < 1:
+            raise HipError("decay_weights: n >= 1 expected")
+        ptrs = [t.data_ptr() for t in self.tensors]
+        if ptrs != self.ptrs:
+            self._tables(ptrs)
+        hip.check(hip.lib().vmg_decay_weights(*self.args, n, hip.stream_ptr()), "vmg_decay_weights")
+        torch.autograd.graph.increment_version(self.weights)
+
+
+def decay_weights(weights: Sequence[torch.Tensor], gammas: Sequence[torch.Tensor], n: int = 1) -> None:
+    """weights[i] <- weights[i] * gammas[i], n times, in place (vmg_decay_weights: each element multiplied n times in a register, the bits of
+    n separate `mul_`).  Dense fp32 tensors of pairwise equal element counts; the list may be of any length.  The weights' autograd version
+    counters move like after an in-place torch op (the pack cache keys on them)."""
+    DecayList(weights, gammas).run(n)
+
+
 class _AccPool:
     """fp32 scatter accumulators at rest are ZERO (cast_clear leaves them so): a buffer is taken for one scatter, rounded + cleared, given back -- no fill pass per
     use.  A buffer that is not given back (an exception in between) is simply dropped.  One stream: every user runs on the current stream, in order."""

@@ -698,7 +698,45 @@ class VMG(nn.Module):
             self.sc_64_16 = nn.Sequential(nn.Conv2d(embed_dim[0], embed_dim[2], 1, 1, 0), nn.GroupNorm(1, embed_dim[2]), nn.ReLU())
             self.sc_32_8 = nn.Sequential(nn.Conv2d(embed_dim[1], embed_dim[3], 1, 1, 0), nn.GroupNorm(1, embed_dim[3]), nn.ReLU())
         self.mlp_wd_param = [p for name, p in self.named_parameters() if ".mlp_blocks." in name]
+        self._forward_calls = 0  # (a plain attribute, not a buffer: the state-dict keys are the reference's)
         self.apply(self._init_weights)
+
+    # ---------------------------------------------------------------------------------------------- call index
+    @property
+    def forward_calls(self) -> int:
+        """Retention decays applied to the mixer weights since construction or the last load_state_dict: forward call k of a freshly loaded
+        model runs on W * Gamma^k (models/function.py:766-768, 779-781), so this is the index of the last call made."""
+        return self._forward_calls
+
+    def load_state_dict(self, *args, **kwargs):
+        """nn.Module.load_state_dict; the call count restarts at 0 (a checkpoint holds weights with whatever decay they had; the reference
+        counts from the load)."""
+        res = super().load_state_dict(*args, **kwargs)
+        self._forward_calls = 0
+        return res
+
+    def advance_calls(self, n: int) -> None:
+        """The weight decay of n more forward calls, applied to every mixer at once (vmg_decay_weights: n rounded multiplies per element, the
+        bits n calls would leave) with the cached weight packs rebuilt; the next forward is then call forward_calls + 1 of the run that made
+        all of them.  The decay cannot be undone exactly: the way back is reloading the checkpoint."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"advance_calls({n}): the retention decay cannot be undone -- reload the checkpoint and advance from 0")
+        if n == 0:
+            return
+        mixers = [m for m in self.modules() if isinstance(m, Enhanced_MorphFCs_decay)]
+        if mixers:
+            FH.decay_weights_and_repack([m.mlp_h[0].weight for m in mixers] + [m.mlp_w[0].weight for m in mixers],
+                                        [m.gamma_h for m in mixers] + [m.gamma_w for m in mixers], n)
+        self._forward_calls += n
+
+    def set_forward_calls(self, k: int) -> None:
+        """advance_calls(k - forward_calls): the next forward is call k + 1 since the load."""
+        k = int(k)
+        if k < self._forward_calls:
+            raise ValueError(f"set_forward_calls({k}): {self._forward_calls} calls have been applied already and the decay cannot be undone -- "
+                             "reload the checkpoint")
+        self.advance_calls(k - self._forward_calls)
 
     @staticmethod
     def _init_weights(m):
@@ -800,6 +838,7 @@ class VMG(nn.Module):
                                         [m.gamma_h for m in mixers] + [m.gamma_w for m in mixers])
             for m in mixers:
                 m._t1_done = True
+        self._forward_calls += 1
         if torch.is_grad_enabled():
             FH.DEFERRED.begin_forward()  # per-pass use counts of the deferred weight gradients (functional._DeferredWgrad)
         # the kernels take fp32 / the module's compute dtype; an enclosing torch.autocast (tools/Trainer.py:132-143) must not
