@@ -231,6 +231,47 @@ def test_swin_one_window_map_matches_oracle(dtype):
         assert err <= (5e-4 if dtype == torch.float32 else 5e-2) * max(1.0, float(gw.abs().max())), f"{k}: {err}"
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("heads,ws", [(8, (4, 8, 8)), (4, (2, 8, 8))], ids=["h8_w4_d18", "h4_w2_d36"])
+def test_swin_decoder_layer_144_channels_fwd_bwd(heads, ws, dtype):
+    """DecoderLayer at the few_levels width, the train_swin workload's: 144 channels / 8 heads / wt 4 (head dimension 18: the MFMA kernels
+    on bf16) and 144 / 4 heads / wt 2 (head dimension 36: the VALU kernel, also on bf16).  Weights by recipe from the module's own
+    state-dict shapes; T = 7 (frame repetition); a 13 x 18 map: remainders 5 and 2, so the shifted block's padded tokens are NOT alone in
+    a mask slab and real queries attend to keys that hold the Linears' biases.  Forward and all gradients vs the oracle, tolerances as in
+    test_swin_decoder_layer_fwd_bwd."""
+    from oracle import recipe as R, vmg_oracle as O
+    from vmg_amd.model import DecoderLayer
+    m = DecoderLayer(144, 2, heads, list(ws), 2, True)
+    sd = R.recipe_state_dict({k: list(v.shape) for k, v in m.state_dict().items()}, 0, None, lambda k: ws)
+    m.load_state_dict(sd, strict=True)
+    m = m.cuda()
+    x = R.seeded((1, 7, 13, 18, 144), 131)
+    if dtype == torch.bfloat16:
+        x = x.to(dtype).float()
+    osd = {k: (v.clone().requires_grad_(True) if v.dtype.is_floating_point else v) for k, v in sd.items()}
+    xo = x.clone().requires_grad_(True)
+    want = O.swin_decoder_layer(osd, "", xo, heads, ws)
+    go = R.seeded(tuple(want.shape), 132)
+    if dtype == torch.bfloat16:
+        go = go.to(dtype).float()
+    leaves = [k for k in sorted(osd) if osd[k].dtype.is_floating_point]
+    wg = torch.autograd.grad(want, [xo] + [osd[k] for k in leaves], go)
+    xd = x.cuda().to(dtype).requires_grad_(True)
+    got = m(xd)
+    got.backward(go.cuda().to(dtype))
+    tol = 2e-4 if dtype == torch.float32 else 3e-2
+    scale = max(1.0, float(want.abs().max()))
+    err = float((got.float().cpu() - want).abs().max())
+    print(f"[swin144] h{heads} wt{ws[0]} {dtype}: out {err / scale:.3e}, dx {float((xd.grad.float().cpu() - wg[0]).abs().max()) / max(1.0, float(wg[0].abs().max())):.3e}")
+    assert err <= tol * scale
+    assert float((xd.grad.float().cpu() - wg[0]).abs().max()) <= tol * max(1.0, float(wg[0].abs().max()))
+    params = dict(m.named_parameters())
+    for k, gw in zip(leaves, wg[1:]):
+        err = float((params[k].grad.cpu() - gw).abs().max())
+        print(f"[swin144]   {k}: {err / max(1.0, float(gw.abs().max())):.3e}")
+        assert err <= (5e-4 if dtype == torch.float32 else 5e-2) * max(1.0, float(gw.abs().max())), f"{k}: {err}"
+
+
 def _fixture(name):
     from oracle import cases as C
     case = C.CASES[name]

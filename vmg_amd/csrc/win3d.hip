@@ -38,8 +38,9 @@ struct Win3dK {
   int sd, sh, sw;   // shift (0 on unshifted blocks)
   int nwd, nwh, nww;  // windows per dimension
   float scale;
-  int dm_lds;  // MFMA backward: the per-slice dS block is kept in LDS and the table gradient gathered from it (fits for wt <= 4)
-  int dbg;  // diagnostics build only (env VMG_WIN3D_DBG): 1 no table-gradient LDS atomics, 2 no pass 2 (dK / dV), 4 no pass 1 (dQ, table)
+  int dm_lds;  // MFMA backward: key slices per dS block in LDS (the table gradient is gathered from it): wt - 1 where that fits, else 2
+  int dm_f32;  // ... and the block then holds fp32 values (wt = 8), as the LDS atomics that used to run there added them
+  int dbg;  // diagnostics build only (env VMG_WIN3D_DBG): 2 no pass 2 (dK / dV), 4 no pass 1 (dQ, table)
 };
 
 template <typename T>
@@ -451,9 +452,13 @@ __global__ __launch_bounds__(256) void win3d_mfma_bwd_kernel(const Win3dK a) {
   // The table gradient dtab[rel] = sum of dS over the (query, key) pairs at that relative position.  One LDS float atomic per element (what the
   // VALU kernel does) was 225 of this kernel's 430 us at the train_swin shape -- ds_add_f32 with 64 distinct addresses retires in ~300 cycles.
   // Instead the four waves store a slice's dS^T (64 queries x N - 64 keys, the bf16 values dQ is computed from) to LDS and every THREAD then owns table entries: it walks the
-  // pairs of its entry (a 2-D diagonal of the block: (8 - |dh|) (8 - |dw|) of them) with plain reads.  Used when the block fits (wt <= 6).
-  const int dm_row = (N - 64) * 2 + 16;
-  char* Dm = a.dm_lds ? reinterpret_cast<char*>(spix + N) : nullptr;
+  // pairs of its entry (a 2-D diagonal of the block: (8 - |dh|) (8 - |dw|) of them) with plain reads.  The block holds a.dm_lds key slices: all
+  // wt - 1 of them up to wt = 7; at wt = 8 that is 3.4 KB more than the LDS has, and a query slice goes through blocks of 2 key slices.
+  // (LDS atomics were the fallback there: four waves adding fp32 dS into the same entries in whatever order they arrive, so the "ordered" table
+  //  gradient of the ABI changed in its last bits from run to run.  The blocks of that case keep fp32: the same numbers are added, in a fixed order.)
+  const int dm_esz = a.dm_f32 ? 4 : 2;
+  const int dm_row = a.dm_lds * 64 * dm_esz + 16;
+  char* Dm = reinterpret_cast<char*>(spix + N);
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int win = blockIdx.x, head = blockIdx.y, d = a.d, c0 = head * d;
@@ -499,43 +504,66 @@ __global__ __launch_bounds__(256) void win3d_mfma_bwd_kernel(const Win3dK a) {
     if (g == 0) { slse[qt] = my_lse; sdel[qt] = delta; }
     const int Rq = wm_rel_q(a.wt, qt);
     f32x4 dqa[2] = {zero4, zero4};
-    for (int tp = 0; tp < NT; tp += 2) {
-      bf16x8 dsf;
-      int tts[2];
+    for (int t0 = 0; t0 < NT; t0 += 4 * a.dm_lds) {  // one block of key slices (tiles t0 .. t1 - 1 of the keys other than slice s)
+      const int t1 = min(NT, t0 + 4 * a.dm_lds);
+      for (int tp = t0; tp < t1; tp += 2) {
+        bf16x8 dsf;
+        int tts[2];
 #pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2) {
-        const int t = tp + h2, tt = t + (t >= 4 * s ? 4 : 0);
-        tts[h2] = tt;
-        const bf16x8 kf = wm_ld8(Ra + (16 * tt + c) * WM_ROW + 16 * g);
-        const bf16x8 vf = wm_ld8(Rb + (16 * tt + c) * WM_ROW + 16 * g);
-        const f32x4 sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, zero4, 0, 0, 0);
-        const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, gof, zero4, 0, 0, 0);
-        const int kt0 = 16 * tt + 4 * g;
-        const int rk = Rq - wm_rel_k(kt0);
-        f32x4 dsv;
+        for (int h2 = 0; h2 < 2; ++h2) {
+          const int t = tp + h2, tt = t + (t >= 4 * s ? 4 : 0);
+          tts[h2] = tt;
+          const bf16x8 kf = wm_ld8(Ra + (16 * tt + c) * WM_ROW + 16 * g);
+          const bf16x8 vf = wm_ld8(Rb + (16 * tt + c) * WM_ROW + 16 * g);
+          const f32x4 sv = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf, zero4, 0, 0, 0);
+          const f32x4 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, gof, zero4, 0, 0, 0);
+          const int kt0 = 16 * tt + 4 * g;
+          const int rk = Rq - wm_rel_k(kt0);
+          f32x4 dsv;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float v = sv[r] * a.scale + tab[rk - r];
-          if (masked && sreg[kt0 + r] != qreg) v -= 100.f;
-          const float p = __expf(v - my_lse);
-          const float ds = p * (dp[r] - delta);
-          dsv[r] = ds;
-#ifdef VMG_DIAG
-          if (!(a.dbg & 1))
-#endif
-          if (!Dm) atomicAdd(&dtab[rk - r], ds);
-          dsf[4 * h2 + r] = (bf16)ds;
+          for (int r = 0; r < 4; ++r) {
+            float v = sv[r] * a.scale + tab[rk - r];
+            if (masked && sreg[kt0 + r] != qreg) v -= 100.f;
+            const float p = __expf(v - my_lse);
+            const float ds = p * (dp[r] - delta);
+            dsv[r] = ds;
+            dsf[4 * h2 + r] = (bf16)ds;
+          }
+          char* dst = Dm + (16 * wave + c) * dm_row + (16 * (t - t0) + 4 * g) * dm_esz;  // (8-byte aligned: two float2 where the block is fp32)
+          if (a.dm_f32) {
+            *reinterpret_cast<float2*>(dst) = make_float2(dsv[0], dsv[1]);
+            *reinterpret_cast<float2*>(dst + 8) = make_float2(dsv[2], dsv[3]);
+          } else {
+            *reinterpret_cast<bf16x4*>(dst) = bf16x4{(bf16)dsv[0], (bf16)dsv[1], (bf16)dsv[2], (bf16)dsv[3]};
+          }
         }
-        if (Dm) *reinterpret_cast<bf16x4*>(Dm + (16 * wave + c) * dm_row + (16 * t + 4 * g) * 2) = bf16x4{(bf16)dsv[0], (bf16)dsv[1], (bf16)dsv[2], (bf16)dsv[3]};
-      }
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        if (u < DU) {
-          const bf16x8 ktf = wm_tr_pair(Ra + (16 * tts[0] + 4 * g + (c >> 2)) * WM_ROW + (16 * u + 4 * (c & 3)) * 2,
-                                        Ra + (16 * tts[1] + 4 * g + (c >> 2)) * WM_ROW + (16 * u + 4 * (c & 3)) * 2);
-          dqa[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf, dqa[u], 0, 0, 0);
+        for (int u = 0; u < 2; ++u) {
+          if (u < DU) {
+            const bf16x8 ktf = wm_tr_pair(Ra + (16 * tts[0] + 4 * g + (c >> 2)) * WM_ROW + (16 * u + 4 * (c & 3)) * 2,
+                                          Ra + (16 * tts[1] + 4 * g + (c >> 2)) * WM_ROW + (16 * u + 4 * (c & 3)) * 2);
+            dqa[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ktf, dsf, dqa[u], 0, 0, 0);
+          }
         }
       }
+      __syncthreads();  // the block of dS^T is complete
+      // entry (i, hh, ww): key slice kd = the (t0 / 4 + i)-th slice other than s; relative position dh = hh - 7 = qh - kh, dw = ww - 7 = qw - kw
+      for (int e = tid; e < ((t1 - t0) >> 2) * 225; e += 256) {
+        const int i = e / 225, rem = e - i * 225, hh = rem / 15, ww = rem - hh * 15;
+        const int ko = (t0 >> 2) + i, kd = ko + (ko >= s ? 1 : 0), dh = hh - 7, dw = ww - 7;
+        const int qh_lo = dh > 0 ? dh : 0, qh_hi = dh < 0 ? 8 + dh : 8, qw_lo = dw > 0 ? dw : 0, qw_hi = dw < 0 ? 8 + dw : 8;
+        float acc = 0.f;
+        for (int qh = qh_lo; qh < qh_hi; ++qh) {
+          const char* row = Dm + (qh * 8) * dm_row + (i * 64 + (qh - dh) * 8 - dw) * dm_esz;  // + qw * (dm_row + dm_esz)
+          if (a.dm_f32) {
+            for (int qw = qw_lo; qw < qw_hi; ++qw) acc += *reinterpret_cast<const float*>(row + qw * (dm_row + 4));
+          } else {
+            for (int qw = qw_lo; qw < qw_hi; ++qw) acc += (float)*reinterpret_cast<const bf16*>(row + qw * (dm_row + 2));
+          }
+        }
+        dtab[(s - kd + a.wt - 1) * 225 + rem] += acc;  // (one thread per entry and block; blocks and slices are separated by the barriers)
+      }
+      __syncthreads();  // before the next block overwrites this one
     }
     // dq = scale * sum_k ds * k (the logits took q scaled); a padded query's gradient goes to the q bias
 #pragma unroll
@@ -554,22 +582,6 @@ __global__ __launch_bounds__(256) void win3d_mfma_bwd_kernel(const Win3dK a) {
           }
         }
       }
-    }
-    if (Dm) {
-      __syncthreads();  // the slice's dS^T block is complete
-      // entry (i, hh, ww): key slice kd = the i-th slice other than s; relative position dh = hh - 7 = qh - kh, dw = ww - 7 = qw - kw
-      for (int e = tid; e < (a.wt - 1) * 225; e += 256) {
-        const int i = e / 225, rem = e - i * 225, hh = rem / 15, ww = rem - hh * 15;
-        const int kd = i + (i >= s ? 1 : 0), dh = hh - 7, dw = ww - 7;
-        const int qh_lo = dh > 0 ? dh : 0, qh_hi = dh < 0 ? 8 + dh : 8, qw_lo = dw > 0 ? dw : 0, qw_hi = dw < 0 ? 8 + dw : 8;
-        float acc = 0.f;
-        for (int qh = qh_lo; qh < qh_hi; ++qh) {
-          const char* row = Dm + (qh * 8) * dm_row + (i * 64 + (qh - dh) * 8 - dw) * 2;  // + qw * (dm_row + 2)
-          for (int qw = qw_lo; qw < qw_hi; ++qw) acc += (float)*reinterpret_cast<const bf16*>(row + qw * (dm_row + 2));
-        }
-        dtab[(s - kd + a.wt - 1) * 225 + rem] += acc;  // (one thread per entry and slice; slices are separated by the barriers)
-      }
-      __syncthreads();  // before the next slice overwrites the block
     }
   }
   __syncthreads();  // every wave is done with the K / V rows; lse / delta of all queries are in LDS
@@ -670,9 +682,9 @@ int launch_win3d_mfma(const Win3dK& k0, hipStream_t st) {
   int lds = 2 * N * WM_ROW + nrel * 4 * (BWD ? 2 : 1) + (BWD ? 2 * N * 4 : 0) + N * 4 + (BWD ? N * 4 : 0) + 16;
   if (BWD) {
     VMG_CHECK((long long)k.B * k.D * k.H * k.W < (1LL << 31), "win3d_attn (MFMA): too many tokens");
-    const int dm = 64 * ((N - 64) * 2 + 16);
-    k.dm_lds = lds + dm <= 160 * 1024 ? 1 : 0;  // (wt = 4: 79 KB in all, two workgroups per CU; wt = 8 does not fit and falls back to LDS atomics)
-    if (k.dm_lds) lds += dm;
+    k.dm_f32 = lds + 64 * ((k.wt - 1) * 128 + 16) <= 160 * 1024 ? 0 : 1;  // (wt = 4: 79 KB in all, two workgroups per CU; wt = 8: fp32 blocks of 2 key slices, 139 KB)
+    k.dm_lds = k.dm_f32 ? 2 : k.wt - 1;
+    lds += 64 * (k.dm_lds * 64 * (k.dm_f32 ? 4 : 2) + 16);
   }
   VMG_CHECK(lds <= 160 * 1024, "win3d_attn (MFMA): %d B of LDS", lds);
   const dim3 grid((unsigned)((long long)k.B * k.nwd * k.nwh * k.nww), k.heads);
