@@ -469,6 +469,26 @@ int vmg_tile_accumulate(int dtype, const void* patch, float* E, float* Wt, int64
                         int top, int bottom, int left, int right, void* stream);
 int vmg_tile_finalize(const float* E, const float* Wt, float* out_f32, unsigned char* out_u8, int64_t n, void* stream);
 
+/* ---- frame scoring: PSNR, PSNR-Y, SSIM, SSIM-Y of uint8 frame pairs (reference: tools/test_reds4.py:194-283 scoring every output frame
+ * with utils/metrics.py:11-26 calculate_psnr, :32-70 structural_similarity and scikit-image's rgb2ycbcr) ------------------------------------
+ * a, b: T frames x 3 channels (R, G, B) x H x W bytes each, addressed as base + f*s[0] + c*s[1] + y*s[2] + x*s[3] with the four element
+ * strides (frame, channel, row, pixel) in the HOST arrays a_strides / b_strides (>= 0): planar (T,3,H,W) frames as vmg_tile_finalize
+ * writes them, interleaved (T,H,W,3) frames as decoded images have them, and any crop or frame subset of either, without a copy.
+ * window: 11 float64 weights on the HOST (the reference's cv2.getGaussianKernel(11, 1.5)); the SSIM map is the "valid" (H-10) x (W-10)
+ * region with C1 = (0.01*255)^2, C2 = (0.03*255)^2.  Y = 16 + (65.481 R + 128.553 G + 24.966 B) / 255 in float64, not rounded.
+ * Per frame f the call leaves
+ *   sse_rgb[f]     int64: the sum of squared differences over R, G and B (exact)
+ *   sums[5f + 0]   float64: the sum of squared Y differences
+ *   sums[5f + 1..4] float64: the sums of the SSIM maps of R, G, B and Y
+ * and the host forms mse = sum / count, PSNR = 20 log10(255 / sqrt(mse)) and SSIM = map sum / ((H-10)(W-10)) (RGB: the mean of the three).
+ * All arithmetic is float64 or integer and nothing is added with atomics: the same input gives the same bits.
+ * ws: vmg_frame_metrics_ws_bytes(T, H, W) bytes of device memory, 8-byte aligned, contents irrelevant (every word read is written first);
+ * reusable by the next call on the stream.  1 <= T <= 65535.  Frames with H < 11 or W < 11 are refused: their SSIM map is empty (the
+ * reference returns NaN with a numpy warning there), and the size query returns 0 for them. */
+int64_t vmg_frame_metrics_ws_bytes(int T, int H, int W);
+int vmg_frame_metrics(const unsigned char* a, const int64_t* a_strides, const unsigned char* b, const int64_t* b_strides, int T, int H, int W,
+                      const double* window, void* ws, int64_t ws_bytes, int64_t* sse_rgb, double* sums, void* stream);
+
 /* ---- MorphFC retention decay, n calls at once (reference: Enhanced_MorphFCs_decay.forward, models/function.py:766-768, 779-781: every
  * forward call multiplies the mlp_h / mlp_w weights by their Gamma buffer in place, in eval mode too -- call k of a freshly loaded model
  * sees W * Gamma^k) --------------------------------------------------------------------------------------------------------------

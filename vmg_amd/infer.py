@@ -372,6 +372,17 @@ def test_clips_max(model: Callable, inputs: torch.Tensor, HR: torch.Tensor, num_
 
 
 @torch.no_grad()
+def to_uint8_device(outputs: torch.Tensor) -> torch.Tensor:
+    """tools/Tester.py:249-250 without the host copy: clamp, *255, round half to even -> torch.uint8 (T, 3, H, W) on the device (the
+    values of to_uint8; what metrics.frame_metrics scores)."""
+    hip.require_cuda(outputs)
+    o = outputs.float().squeeze().contiguous()
+    if o.dim() == 3:  # (a single frame: .squeeze() took its T axis too)
+        o = o.unsqueeze(0)
+    return _finalize(o, torch.ones_like(o), want_u8=True)
+
+
+@torch.no_grad()
 def to_uint8(outputs: torch.Tensor) -> np.ndarray:
     """tools/Tester.py:249-250: clamp, *255, round half to even, uint8, (T, H, W, C) on the host."""
     hip.require_cuda(outputs)

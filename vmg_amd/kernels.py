@@ -1282,3 +1282,34 @@ def resblock_chain_forward_q8(y0: torch.Tensor, pw1, b1, pw2, b2, r_scaling: flo
     d.r_scaling = r_scaling
     hip.check(hip.lib().vmg_resblock_chain_fwd_q8(ctypes.byref(d), hip.stream_ptr()), "vmg_resblock_chain_fwd_q8")
     return ys, ts
+
+
+def gaussian_window(ksize: int = 11, sigma: float = 1.5):
+    """cv2.getGaussianKernel(ksize, sigma) for the sizes that have no fixed table: exp(-x^2 / (2 sigma^2)) in float64, scaled by the
+    reciprocal of the sum (utils/metrics.py:56)."""
+    import math
+    t = [math.exp(-0.5 / (sigma * sigma) * (i - (ksize - 1) * 0.5) ** 2) for i in range(ksize)]
+    s = 1.0 / sum(t)
+    return [v * s for v in t]
+
+
+def frame_metrics_sums(a: torch.Tensor, b: torch.Tensor, ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vmg_frame_metrics on two uint8 (T, 3, H, W) VIEWS of any strides (planar or interleaved storage, crops, frame subsets): returns the
+    device tensors sse_rgb (T) int64 and sums (T, 5) float64 = [SSE of Y, SSIM map sums of R, G, B, Y].  Nothing is synchronised."""
+    hip.require_cuda(a, b, ws)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise HipError(f"frame_metrics: uint8 frames expected, got {a.dtype} and {b.dtype}")
+    if a.dim() != 4 or a.shape[1] != 3 or a.shape != b.shape:
+        raise HipError(f"frame_metrics: two (T, 3, H, W) views of one shape expected, got {tuple(a.shape)} and {tuple(b.shape)}")
+    T, _, H, W = a.shape
+    lib = hip.lib()
+    need = int(lib.vmg_frame_metrics_ws_bytes(T, H, W))
+    if ws is None and need > 0:
+        ws = torch.empty(need, dtype=torch.uint8, device=a.device)
+    sse = torch.empty(T, dtype=torch.int64, device=a.device)
+    sums = torch.empty((T, 5), dtype=torch.float64, device=a.device)
+    sa, sb = (ctypes.c_int64 * 4)(*a.stride()), (ctypes.c_int64 * 4)(*b.stride())
+    win = (ctypes.c_double * 11)(*gaussian_window(11, 1.5))
+    hip.check(lib.vmg_frame_metrics(a.data_ptr(), sa, b.data_ptr(), sb, T, H, W, win, ws.data_ptr() if ws is not None else None,
+                                    ws.numel() if ws is not None else 0, sse.data_ptr(), sums.data_ptr(), hip.stream_ptr()), "vmg_frame_metrics")
+    return sse, sums
