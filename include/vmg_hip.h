@@ -315,6 +315,8 @@ int vmg_space_depth_ln_bwd(int dtype, int mode, const void* dy, const void* x, c
  *                        op 4 GATE_FWD o0 = (p0 + p1) * tanh(p1)
  *                        op 5 GATE_BWD p0 = dy, p1 = x, p2 = y:  o0 = dy*tanh(y);  o1 = dy*(tanh(y) + (x+y)*(1 - tanh(y)^2))
  *                        op 7 SCALE    o0 = p0 * coef[g,c] * s   (gradient of the DropPath residual w.r.t. the dropped branch, function.py:1212-1217)
+ *                        Every pointer an op reads or writes must be present and 16-byte aligned (checked on the host; ops 6, 8, 9: tab_ops.hip).
+ *                        vmg_group_reduce takes c3 only together with b.
  * ---------------------------------------------------------------------------------------------- */
 int64_t vmg_group_reduce_ws_bytes(void);
 int vmg_group_reduce(int dtype, const void* a, const void* b, const void* c3, float* out, int G, int64_t R, int C, int mode, float scale,

@@ -513,6 +513,7 @@ extern "C" int vmg_group_reduce(int dtype, const void* a, const void* b, const v
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "group_reduce: bad dtype");
   VMG_CHECK(a && out && ws && G > 0 && R > 0 && C > 0 && (C & 1) == 0 && C <= 512, "group_reduce: bad arguments (C even, <= 512)");
   VMG_CHECK(mode == 0 || (mode == 1 && b), "group_reduce: mode 1 needs b");
+  VMG_CHECK(b || !c3, "group_reduce: c3 needs b (the sum of two tensors is a + b)");
   const int chunks = gr_chunks(G, R);
   VMG_CHECK((int64_t)G * chunks * C * (int64_t)sizeof(float) <= ws_bytes, "group_reduce: workspace too small (vmg_group_reduce_ws_bytes)");
   hipStream_t st = (hipStream_t)stream;
@@ -562,9 +563,21 @@ extern "C" int vmg_group_reduce3(int dtype, const void* a, const void* b0, const
 extern "C" int vmg_tab_elementwise(int dtype, int op, const void* p0, const void* p1, const void* p2, const float* coef, const float* add,
                                    float s, void* o0, void* o1, void* o2, int64_t rows, int64_t R, int C, void* stream) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "tab_elementwise: bad dtype");
-  VMG_CHECK(op >= 0 && op <= 9 && p0 && o0 && rows > 0 && R > 0 && C > 0, "tab_elementwise: bad arguments");
+  VMG_CHECK(op >= 0 && op <= 9 && p0 && o0 && rows > 0 && R > 0 && rows % R == 0 && C > 0, "tab_elementwise: bad arguments");
   const int vn = dtype == VMG_BF16 ? 8 : 4;
   VMG_CHECK(C % vn == 0, "tab_elementwise: C must be a multiple of %d", vn);
+  // what each op dereferences (tab_ew_kernel): bit 0 p1, 1 p2, 2 coef, 3 add, 4 o1, 5 o2; p0 and o0 always.  OP_AFFINE2's p1 is optional.
+  static const unsigned char uses[10] = {/*CA_FWD*/ 1 | 4,      /*CA_BWD*/ 4 | 8 | 16, /*MIX_FWD*/ 1 | 2 | 4,      /*MIX_BWD*/ 4 | 8 | 16 | 32,
+                                         /*GATE_FWD*/ 1,        /*GATE_BWD*/ 1 | 2 | 16, /*AFFINE2*/ 4 | 8,        /*SCALE*/ 4,
+                                         /*GATE_RES_FWD*/ 1 | 2 | 4, /*GATE_RES_BWD*/ 1 | 2 | 4 | 16};
+  const void* const ptrs[6] = {p1, p2, coef, add, o1, o2};
+  static const char* const names[6] = {"p1", "p2", "coef", "add", "o1", "o2"};
+  VMG_CHECK((((uintptr_t)p0 | (uintptr_t)o0) % 16) == 0, "tab_elementwise: pointers must be 16-byte aligned");
+  for (int i = 0; i < 6; ++i) {
+    const bool used = (uses[op] >> i) & 1;
+    VMG_CHECK(!used || ptrs[i], "tab_elementwise: op %d needs %s", op, names[i]);
+    VMG_CHECK(!(used || (op == OP_AFFINE2 && i == 0)) || (uintptr_t)ptrs[i] % 16 == 0, "tab_elementwise: %s must be 16-byte aligned", names[i]);
+  }
   const long long total = rows * (C / vn);
   const int blocks = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
   hipStream_t st = (hipStream_t)stream;

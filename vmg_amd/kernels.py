@@ -1062,10 +1062,26 @@ def group_reduce3(a: torch.Tensor, b0: torch.Tensor, b1: torch.Tensor, b2: torch
     return out
 
 
+# per op: coefficients per (group, channel) in `coef` (0: no coef), whether `add` (G, C) is read, outputs
+_TAB_EW = {OP_CA_FWD: (1, False, 1), OP_CA_BWD: (1, True, 2), OP_MIX_FWD: (3, False, 1), OP_MIX_BWD: (3, True, 3), OP_GATE_FWD: (0, False, 1),
+           OP_GATE_BWD: (0, False, 2), OP_AFFINE2: (2, True, 1), OP_SCALE: (1, False, 1), OP_GATE_RES_FWD: (1, False, 1), OP_GATE_RES_BWD: (1, False, 2)}
+
+
 def tab_elementwise(op: int, p0, p1=None, p2=None, coef=None, add=None, s: float = 1.0, G: int = 1, nout: int = 1):
     hip.require_cuda(p0, p1, p2, coef, add)
+    if op not in _TAB_EW:
+        raise HipError(f"tab_elementwise: unknown op {op}")
+    ncoef, has_add, op_nout = _TAB_EW[op]
     C = p0.shape[-1]
     rows = p0.numel() // C
+    if G <= 0 or rows % G:
+        raise HipError(f"tab_elementwise: {rows} rows do not split into G = {G} groups")
+    if nout != op_nout:
+        raise HipError(f"tab_elementwise: op {op} writes {op_nout} outputs, not {nout}")
+    if ncoef and (coef is None or coef.numel() != G * C * ncoef):
+        raise HipError(f"tab_elementwise: op {op} needs coef of G*C*{ncoef} = {G * C * ncoef} elements")
+    if has_add and (add is None or add.numel() != G * C):
+        raise HipError(f"tab_elementwise: op {op} needs add of G*C = {G * C} elements")
     for t in (p0, p1, p2):
         if t is not None and (not t.is_contiguous() or t.shape != p0.shape or t.dtype != p0.dtype):
             raise HipError("tab_elementwise: contiguous operands of one shape / dtype expected")
