@@ -249,12 +249,13 @@ extern "C" int vmg_warp_bilinear_bwd(int dtype, const void* x, const float* flow
                                      int H, int W, int C, void* stream) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "warp_bwd: bad dtype");
   VMG_CHECK(x && flow && dy && dx_acc && dflow && N > 0 && H > 0 && W > 0 && C > 0, "warp_bwd: bad arguments");
+  // the forward's conditions (a tensor it refused has no backward); the bf16 pair loads need C even and 4-byte alignment, which these imply
   const int vn = dtype == VMG_BF16 ? 8 : 4;
-  (void)vn;
+  VMG_CHECK(C % vn == 0, "warp_bwd: C must be a multiple of %d", vn);
+  VMG_CHECK(((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx_acc) % 16 == 0, "warp_bwd: pointers must be 16-byte aligned");
   const long long total = (long long)N * H * W * 64;  // one wave per pixel
   hipStream_t st = (hipStream_t)stream;
   if (dtype == VMG_BF16) {
-    VMG_CHECK(C % 2 == 0 && ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx_acc) % 4 == 0, "warp_bwd: bf16 needs an even channel count and 4-byte aligned tensors");
     hipLaunchKernelGGL(warp_bilinear_bwd_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, st, (const bf16*)x, flow, (const bf16*)dy, (float*)dx_acc, dflow, N, H, W, C);
   } else {
     hipLaunchKernelGGL(warp_bilinear_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, st, (const float*)x, flow, (const float*)dy, (float*)dx_acc, dflow, N, H, W, C);

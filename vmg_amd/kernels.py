@@ -939,7 +939,12 @@ def warp_bilinear_forward(x: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
 
 def warp_bilinear_backward(x: torch.Tensor, flow: torch.Tensor, dy: torch.Tensor):
     """-> (dx in x's dtype, dflow fp32)."""
+    hip.require_cuda(x, flow, dy)
     n, h, w, c = x.shape
+    if not x.is_contiguous() or flow.dtype != torch.float32 or not flow.is_contiguous() or tuple(flow.shape) != (n, h, w, 2):
+        raise HipError("warp: x must be contiguous (n,h,w,c), flow contiguous fp32 (n,h,w,2)")
+    if dy.dtype != x.dtype or tuple(dy.shape) != (n, h, w, c):
+        raise HipError(f"warp_bilinear_backward: dy must have x's shape and dtype, got {tuple(dy.shape)} {dy.dtype}")
     dy = dy.contiguous()
     # fp32 sums for bf16 tensors too, rounded once: the accumulator comes from the pool of zeroed buffers and goes back cleared by the rounding pass
     pooled = x.dtype != torch.float32 and (n * h * w * c) % 4 == 0
@@ -979,6 +984,17 @@ def warp_nearest_planes(loc: torch.Tensor, flow: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _ltam_check_tables(rpe, decay, heads, wh, ww):
+    """The kernels index rpe as [heads][wh*ww][wh*ww] and decay as [heads]: a table made for another window would be read out of bounds."""
+    wq = wh * ww
+    if rpe.dtype != torch.float32 or decay.dtype != torch.float32 or not rpe.is_contiguous():
+        raise HipError("ltam: rpe / decay must be fp32")
+    if tuple(rpe.shape) != (heads, wq, wq):
+        raise HipError(f"ltam: rpe must be (heads, wh*ww, wh*ww) = {(heads, wq, wq)}, got {tuple(rpe.shape)}")
+    if decay.numel() != heads or not decay.is_contiguous():
+        raise HipError(f"ltam: decay must hold {heads} contiguous values, got {tuple(decay.shape)}")
+
+
 def ltam_forward(q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
     hip.require_cuda(q, loc, rpe, decay, *keys, *vals)
     n, h, w, c = q.shape
@@ -988,8 +1004,7 @@ def ltam_forward(q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
         raise HipError("ltam: q / keys / vals must be contiguous (n,h,w,c) tensors of one dtype")
     if loc.dtype != torch.float32 or tuple(loc.shape) != (n, 2 * t, h, w) or not loc.is_contiguous():
         raise HipError(f"ltam: loc must be contiguous fp32 (n,2t,h,w), got {tuple(loc.shape)}")
-    if rpe.dtype != torch.float32 or decay.dtype != torch.float32 or not rpe.is_contiguous():
-        raise HipError("ltam: rpe / decay must be fp32")
+    _ltam_check_tables(rpe, decay, heads, wh, ww)
     out = torch.empty_like(q)
     lse = torch.empty((n, h, w, heads), dtype=torch.float32, device=q.device)
     hip.check(hip.lib().vmg_ltam_fwd(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), rpe.data_ptr(),
@@ -1003,8 +1018,17 @@ def ltam_backward(q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww,
     key-frame an existing fp32 accumulator to scatter into (the gradient of a frame that several calls attend to is summed by the kernel's
     atomics, see functional.grad_bank), or None for a fresh zeroed one.  drpe_into: an fp32 tensor of rpe's shape to ADD the table gradient into (the
     parameter's .grad in the deferred weight-gradient mode) instead of a fresh zeroed one."""
+    hip.require_cuda(q, loc, rpe, decay, out, lse, dout, *keys, *vals)
     n, h, w, c = q.shape
     t = len(keys)
+    _ltam_check_tables(rpe, decay, heads, wh, ww)
+    for nm, a in (("out", out), ("dout", dout)):
+        if a.dtype != q.dtype or tuple(a.shape) != (n, h, w, c):
+            raise HipError(f"ltam_backward: {nm} must have q's shape and dtype, got {tuple(a.shape)} {a.dtype}")
+    if not out.is_contiguous():
+        raise HipError("ltam_backward: out must be contiguous")
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (n, h, w, heads) or not lse.is_contiguous():
+        raise HipError(f"ltam_backward: lse must be contiguous fp32 (n,h,w,heads), got {tuple(lse.shape)} {lse.dtype}")
     dout = dout.contiguous()
     dq = torch.empty_like(q)
     dk = list(dk_into) if dk_into is not None else [None] * t
