@@ -491,6 +491,26 @@ int64_t vmg_frame_metrics_ws_bytes(int T, int H, int W);
 int vmg_frame_metrics(const unsigned char* a, const int64_t* a_strides, const unsigned char* b, const int64_t* b_strides, int T, int H, int W,
                       const double* window, void* ws, int64_t ws_bytes, int64_t* sse_rgb, double* sums, void* stream);
 
+/* ---- LR frames from HR frames: MATLAB-style antialiased bicubic downscale (reference: datasets/generate_LR.py:32-37 calling
+ * utils/image_resize.py imresize_np(img, 1 / scale, True), and cv2.imwrite's rounding of the result) ----------------------------------------
+ * src: T frames x 3 channels x H x W bytes, addressed through the four element strides (frame, channel, row, pixel) of the HOST array
+ * `strides` (>= 0) exactly as the frames of the scoring call above: planar or interleaved storage, crops and frame subsets are read in place.
+ * scale: 2, 3 or 4; H and W multiples of it and at least 4 * scale (a smaller frame would mirror more than once).  Per axis, output sample
+ * o (0-based) sits at the 1-based input coordinate u = (o + 1) scale + 0.5 (1 - scale) and is the sum over the 4 * scale + 2 samples
+ * j = floor(u - 2 scale) + p of k((u - j) / scale) x[j] / (sum of the k), k = Keys' cubic with a = -0.5; samples outside the frame are mirrored
+ * with edge repeat (-1 -> 0, H -> H - 1).  Rows first, then columns, both in float64 in a fixed order: the same input gives the same bits.
+ * out: contiguous planar (T, 3, H / scale, W / scale), out_type one of
+ *   VMG_LR_U8    min(255, max(0, rint(v))), round half to even: the byte cv2.imwrite stores
+ *   VMG_LR_F32   that byte / 255 as the correctly rounded fp32 quotient (what a dataset feeds the network after reading the image)
+ *   VMG_LR_BF16  the fp32 value rounded to bf16 (nearest even)
+ *   VMG_LR_F64   v itself on the 0..255 scale, not rounded and not clamped
+ * One launch, no workspace.  1 <= T <= 65535. */
+#define VMG_LR_U8 0
+#define VMG_LR_F32 1
+#define VMG_LR_BF16 2
+#define VMG_LR_F64 3
+int vmg_bicubic_down(const unsigned char* src, const int64_t* strides, int T, int H, int W, int scale, int out_type, void* out, void* stream);
+
 /* ---- MorphFC retention decay, n calls at once (reference: Enhanced_MorphFCs_decay.forward, models/function.py:766-768, 779-781: every
  * forward call multiplies the mlp_h / mlp_w weights by their Gamma buffer in place, in eval mode too -- call k of a freshly loaded model
  * sees W * Gamma^k) --------------------------------------------------------------------------------------------------------------

@@ -1353,3 +1353,26 @@ def frame_metrics_sums(a: torch.Tensor, b: torch.Tensor, ws: Optional[torch.Tens
     hip.check(lib.vmg_frame_metrics(a.data_ptr(), sa, b.data_ptr(), sb, T, H, W, win, ws.data_ptr() if ws is not None else None,
                                     ws.numel() if ws is not None else 0, sse.data_ptr(), sums.data_ptr(), hip.stream_ptr()), "vmg_frame_metrics")
     return sse, sums
+
+
+LR_OUT_TYPES = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2, torch.float64: 3}  # VMG_LR_* of include/vmg_hip.h
+
+
+def bicubic_down(view: torch.Tensor, s: int, out_dtype: torch.dtype = torch.uint8) -> torch.Tensor:
+    """vmg_bicubic_down on a uint8 (T, 3, H, W) VIEW of any strides (planar or interleaved storage, crops, frame subsets): the contiguous
+    planar (T, 3, H/s, W/s) result as out_dtype (uint8, float32, bfloat16: the stored byte, / 255 for the float types; float64: unrounded,
+    0..255).  One launch, no workspace, nothing is synchronised."""
+    hip.require_cuda(view)
+    if view.dtype != torch.uint8:
+        raise HipError(f"bicubic_down: uint8 frames expected, got {view.dtype}")
+    if view.dim() != 4 or view.shape[1] != 3:
+        raise HipError(f"bicubic_down: a (T, 3, H, W) view expected, got {tuple(view.shape)}")
+    if out_dtype not in LR_OUT_TYPES:
+        raise HipError(f"bicubic_down: out_dtype must be uint8, float32, bfloat16 or float64, got {out_dtype}")
+    s = int(s)
+    T, _, H, W = view.shape
+    out = torch.empty((T, 3, H // s if s > 0 else 0, W // s if s > 0 else 0), dtype=out_dtype, device=view.device)
+    strides = (ctypes.c_int64 * 4)(*view.stride())
+    hip.check(hip.lib().vmg_bicubic_down(view.data_ptr(), strides, T, H, W, s, LR_OUT_TYPES[out_dtype], out.data_ptr(), hip.stream_ptr()),
+              "vmg_bicubic_down")
+    return out
