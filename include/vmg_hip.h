@@ -511,6 +511,30 @@ int vmg_frame_metrics(const unsigned char* a, const int64_t* a_strides, const un
 #define VMG_LR_F64 3
 int vmg_bicubic_down(const unsigned char* src, const int64_t* strides, int T, int H, int W, int scale, int out_type, void* out, void* stream);
 
+/* ---- Training batches from resident frames: N crops, flipped / transposed per crop (reference: data/REDS.py:188-215 and
+ * data/Vimeo.py:179-206 -- the random crop, augment's [:, ::-1], [::-1, :] and transpose(1, 0, 2), BGR -> RGB, HWC -> CHW, and the / 255 of
+ * read_img) -------------------------------------------------------------------------------------------------------------------------
+ * frames: DEVICE array of N absolute addresses, the first byte of each crop's own H x W x 3 uint8 frame.  strides: HOST array of the three
+ * BYTE strides (row, pixel, channel; >= 0) all frames share: interleaved (H, W, 3), planar (3, H, W) and windows of either are just strides.
+ * desc: DEVICE array of N x int32 {y0, x0, flags}, flags = hflip | vflip << 1 | rot << 2.  With (i, j) = (c, r) if rot, else (r, c), output
+ * pixel (r, c) of channel k is the frame's byte at row y0 + (vflip ? ch - 1 - i : i), column x0 + (hflip ? cw - 1 - j : j), channel
+ * (channel_reverse ? 2 - k : k).  rot needs ch == cw.
+ * THE KERNEL TRUSTS THE DESCRIPTORS: they live on the device, so the call cannot refuse them.  0 <= y0 <= H - ch, 0 <= x0 <= W - cw and
+ * rot only with square crops are the caller's to guarantee (vmg_amd.batches.assemble refuses them on the host); the kernel clamps an origin
+ * into that range and ignores rot on a non-square crop rather than leave the frame, and reports neither.
+ * out: contiguous planar (N, 3, ch, cw), out_type one of
+ *   VMG_CROP_U8    the bytes themselves
+ *   VMG_CROP_F32   byte / 255 as the correctly rounded fp32 quotient (numpy's astype(float32) / 255., data/REDS.py:116)
+ *   VMG_CROP_BF16  that fp32 value rounded to bf16 (nearest even)
+ * The call itself refuses, with a message and without a launch: a null pointer, N <= 0, ch or cw <= 0 or larger than the frame, an unknown
+ * out_type, an output not aligned to its element, a negative stride, and more than 2^24 - 1 tiles of 32 x 32 output pixels in one call.
+ * One launch, no workspace; the kernel moves bytes and divides, so equal inputs give equal bits. */
+#define VMG_CROP_U8 0
+#define VMG_CROP_F32 1
+#define VMG_CROP_BF16 2
+int vmg_crop_batch(const void* const* frames, const int64_t* strides, const int* desc, int N, int H, int W, int ch, int cw, int channel_reverse,
+                   int out_type, void* out, void* stream);
+
 /* ---- MorphFC retention decay, n calls at once (reference: Enhanced_MorphFCs_decay.forward, models/function.py:766-768, 779-781: every
  * forward call multiplies the mlp_h / mlp_w weights by their Gamma buffer in place, in eval mode too -- call k of a freshly loaded model
  * sees W * Gamma^k) --------------------------------------------------------------------------------------------------------------

@@ -169,6 +169,7 @@ SIGNATURES = {
     "vmg_frame_metrics": (c_int, [c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_int, c_int, c_int, POINTER(ctypes.c_double), c_void_p, c_int64,
                                   c_void_p, c_void_p, c_void_p]),
     "vmg_bicubic_down": (c_int, [c_void_p, POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "vmg_crop_batch": (c_int, [c_void_p, POINTER(c_int64), c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vmg_decay_weights": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int64), c_int, c_int, c_void_p]),
     "vmg_conv_debug_stamps": (c_int, [c_void_p]),
     "vmg_create": (c_void_p, [c_int]),

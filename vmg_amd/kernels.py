@@ -1376,3 +1376,28 @@ def bicubic_down(view: torch.Tensor, s: int, out_dtype: torch.dtype = torch.uint
     hip.check(hip.lib().vmg_bicubic_down(view.data_ptr(), strides, T, H, W, s, LR_OUT_TYPES[out_dtype], out.data_ptr(), hip.stream_ptr()),
               "vmg_bicubic_down")
     return out
+
+
+CROP_OUT_TYPES = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}  # VMG_CROP_* of include/vmg_hip.h
+
+
+def crop_batch(frames: torch.Tensor, strides: Sequence[int], desc: torch.Tensor, H: int, W: int, ch: int, cw: int, channel_reverse: bool,
+               out: torch.Tensor) -> torch.Tensor:
+    """vmg_crop_batch: frames = device int64 (N) absolute addresses of uint8 H x W x 3 frames that share the byte strides (row, pixel,
+    channel); desc = device int32 (N, 3) {y0, x0, hflip | vflip << 1 | rot << 2}; out = contiguous (N, 3, ch, cw) or any contiguous tensor
+    of that many uint8 / float32 / bfloat16 elements, written in place.  The kernel trusts the descriptors (vmg_amd.batches checks them
+    on the host).  One launch, no workspace, nothing is synchronised."""
+    hip.require_cuda(frames, desc, out)
+    if frames.dtype != torch.int64 or frames.dim() != 1 or not frames.is_contiguous():
+        raise HipError(f"crop_batch: a contiguous int64 (N) table of frame addresses expected, got {frames.dtype} {tuple(frames.shape)}")
+    N = frames.shape[0]
+    if desc.dtype != torch.int32 or tuple(desc.shape) != (N, 3) or not desc.is_contiguous():
+        raise HipError(f"crop_batch: a contiguous int32 ({N}, 3) descriptor table expected, got {desc.dtype} {tuple(desc.shape)}")
+    if out.dtype not in CROP_OUT_TYPES:
+        raise HipError(f"crop_batch: the output must be uint8, float32 or bfloat16, got {out.dtype}")
+    if not out.is_contiguous() or out.numel() != N * 3 * ch * cw:
+        raise HipError(f"crop_batch: a contiguous output of {N} x 3 x {ch} x {cw} elements expected, got {tuple(out.shape)}")
+    st = (ctypes.c_int64 * 3)(*[int(s) for s in strides])
+    hip.check(hip.lib().vmg_crop_batch(frames.data_ptr(), st, desc.data_ptr(), N, int(H), int(W), int(ch), int(cw), int(bool(channel_reverse)),
+                                       CROP_OUT_TYPES[out.dtype], out.data_ptr(), hip.stream_ptr()), "vmg_crop_batch")
+    return out
