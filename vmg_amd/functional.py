@@ -6,6 +6,7 @@ libvmg_hip.so.  Activations are channels-last (..., C); parameters stay fp32 in 
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional, Sequence
 
 import torch
@@ -13,6 +14,7 @@ import torch
 from . import hip
 from . import kernels as K
 from .hip import HipError
+from .wgrad import DEFERRED, _wgrad_entries, _wgrad_now, flush_deferred_wgrads, recorded, set_wgrad_mode  # noqa: F401  (the deferred weight gradients: re-exported)
 
 class _Fn(torch.autograd.Function):
     """torch.autograd.Function whose apply() skips the functorch bookkeeping (setup_context probing, dead-wrapper unwrapping of every
@@ -277,282 +279,6 @@ def _pad_channels(t: torch.Tensor, mult: int = 8) -> torch.Tensor:
     return torch.nn.functional.pad(t, (0, _pad_to(c, mult) - c))
 
 
-# ---------------------------------------------------------------------------------------------------------
-# deferred, batched weight gradients
-#
-# The recurrence applies one conv module to every frame in both directions (2T uses per step).  A weight gradient
-# per use has K = B*H*W pixels against a 144x144x9 fp32 output, so its float-atomic epilogue dominates.  Instead,
-# backward only RECORDS (input, output-gradient) pairs; when the last use of a parameter has been seen the pairs
-# are summed by ONE batched launch straight into param.grad (no zero-fill, no autograd accumulate kernels).
-# 288 GB of HBM make keeping the pairs alive until then a non-issue.
-# ---------------------------------------------------------------------------------------------------------
-class _DeferredWgrad:
-    """mode 'autograd' (default): every conv / Linear backward computes its weight gradient at once and returns it through
-    autograd -- standard semantics, so torch DistributedDataParallel, GradScaler, clip_grad_norm_ and hooks all see it.
-    mode 'deferred' (vmg_amd.train.TrainStep switches it on): backward only records the pairs, see above.
-
-    Use counts are kept PER FORWARD PASS (a generation token taken in VMG.forward and stored in each autograd node), so
-    a grad-enabled forward that is never back-propagated (an eval / logging call, a batch dropped after an exception)
-    cannot leave counts behind that would silence a later step; and whatever is still pending when a backward() call ends
-    is flushed by an end-of-backward engine callback, so no caller has to flush explicitly."""
-
-    KEEP_GENERATIONS = 8
-
-    def __init__(self):
-        self.mode = "autograd"
-        self.gen = 0
-        self.uses = {}      # (generation, id(param)) -> outstanding forward uses
-        self.pending = {}   # id(param) -> [weight, bias, entries]
-        self.callbacks = []  # called with each parameter whose .grad has just been completed
-        self.managed = set()  # ids of the parameters (weights and their biases) whose gradient is completed HERE, not by autograd
-        self._queued = False
-        self.ready = []     # [weight, bias, entries] whose last use has been seen, not batchable: launched by drain()
-        self.waiting = {}   # multi-launch signature -> complete parameters waiting for company (launched at eight, or by drain())
-        self.hold = 0       # > 0: a node that completes many parameters at once (a residual chain) is collecting them
-        self.extra = {}     # (generation, id(param)) -> outstanding contributions of OTHER nodes to a managed bias (note_extra)
-        self.held = {}      # id(param) -> param whose weight-gradient launch is done while such a contribution is still outstanding
-        self.bw_gen = 0     # generation of the backward pass that is running (taken from the recorded entries)
-
-    def begin_forward(self):
-        """New top-level forward pass: a fresh generation; counts of passes older than KEEP_GENERATIONS are dropped."""
-        self.gen += 1
-        if self.uses or self.extra:
-            lo = self.gen - self.KEEP_GENERATIONS
-            for d in (self.uses, self.extra):
-                for key in [k for k in d if k[0] < lo]:
-                    del d[key]
-
-    def note_use(self, weight, bias=None) -> int:
-        key = (self.gen, id(weight))
-        self.uses[key] = self.uses.get(key, 0) + 1
-        self.managed.add(id(weight))
-        if bias is not None:
-            self.managed.add(id(bias))
-        return self.gen
-
-    # -- small parameters (LayerNorm affine, squeeze-excite MLPs): in mode 'deferred' their backward kernels add straight into .grad
-    #    (no zero-filled temporaries, no AccumulateGrad add per parameter)
-    def direct(self, *params) -> bool:
-        return self.mode == "deferred" and all(p is not None and p.requires_grad and p.is_leaf for p in params)
-
-    def note_params(self, *params) -> int:
-        for p in params:
-            key = (self.gen, id(p))
-            self.uses[key] = self.uses.get(key, 0) + 1
-            self.managed.add(id(p))
-        return self.gen
-
-    # the three steps of a node with such parameters: claim() in its forward, into() and done() in its backward
-    def claim(self, ctx, *params):
-        """Decides whether the node's backward adds straight into .grad (ctx.direct) and, if so, counts this use of the parameters."""
-        ctx.direct = self.direct(*params)
-        if ctx.direct:
-            ctx.params, ctx.gen = params, self.note_params(*params)
-
-    def into(self, ctx):
-        """The parameters' .grad buffers for the backward kernel to add into, or None: the gradients are returned through autograd."""
-        return tuple(self.grad_of(p) for p in ctx.params) if ctx.direct else None
-
-    def done(self, ctx):
-        """This use of the parameters is complete, whether the backward kernel ran or the node had nothing to add."""
-        if ctx.direct:
-            self.written(ctx.gen, *ctx.params)
-
-    # -- a bias that a Linear / conv manages (its gradient is written by the deferred weight-gradient launch) may ALSO receive gradient from
-    #    another node -- the 3-D window attention's q / kv biases, through the zero-padded positions (models/swin_3d.py: the padding is added
-    #    before the Linears, so a padded token's q is the bias).  That node adds straight into .grad and the bias counts as complete only
-    #    when BOTH have written: reporting it at the weight-gradient launch alone let the gradient reducer start the bucket's all-reduce
-    #    while the attention backward's add was still to come (replicas diverge).
-    def note_extra(self, *params) -> int:
-        for p in params:
-            key = (self.gen, id(p))
-            self.extra[key] = self.extra.get(key, 0) + 1
-            self.managed.add(id(p))
-        return self.gen
-
-    def extra_written(self, gen: int, *params):
-        for p in params:
-            key = (gen, id(p))
-            left = self.extra.get(key, 1) - 1
-            if left > 0:
-                self.extra[key] = left
-                continue
-            self.extra.pop(key, None)
-            if self.held.pop(id(p), None) is not None:
-                for cb in self.callbacks:
-                    cb(p)
-
-    def _complete(self, p):
-        """The deferred launch that writes p's gradient has been issued: report p, unless another node still owes it a contribution."""
-        if self.extra and self.extra.get((self.bw_gen, id(p)), 0) > 0:
-            self.held[id(p)] = p
-            return
-        for cb in self.callbacks:
-            cb(p)
-
-    @staticmethod
-    def grad_of(p: torch.Tensor) -> torch.Tensor:
-        if p.grad is None:
-            p.grad = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
-        return p.grad
-
-    def written(self, gen: int, *params):
-        for p in params:
-            key = (gen, id(p))
-            left = self.uses.get(key, 1) - 1
-            if left <= 0:
-                self.uses.pop(key, None)
-                for cb in self.callbacks:
-                    cb(p)
-            else:
-                self.uses[key] = left
-
-    def add(self, weight, bias, srcs, src_ch, dpre, ks, N, H, W, scale: float = 1.0, gen: int = 0, o0: int = 0):
-        """o0: first output channel of this use (a group of a grouped convolution writes rows o0 .. o0 + dpre channels of the gradient)."""
-        ent = self.pending.setdefault(id(weight), [weight, bias, []])
-        ent[2].append((srcs, tuple(src_ch), dpre, ks, N, H, W, float(scale), int(o0)))
-        self.bw_gen = gen
-        if not self._queued:  # whatever is still pending when this backward() call ends is completed then
-            torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
-            self._queued = True
-        key = (gen, id(weight))
-        left = self.uses.get(key, 1) - 1
-        if left <= 0:
-            self.uses.pop(key, None)
-            self.flush(weight)
-        else:
-            self.uses[key] = left
-
-    def _end_of_backward(self):
-        self._queued = False
-        for key in list(self.pending):
-            self.flush(self.pending[key][0])
-        self.hold = 0
-        self.drain()
-        if self.held:  # (a contribution that never came -- its node was not part of this backward: the gradient is what it is)
-            held, self.held = self.held, {}
-            for p in held.values():
-                for cb in self.callbacks:
-                    cb(p)
-
-    def flush(self, weight):
-        ent = self.pending.pop(id(weight), None)
-        if ent is None:
-            return
-        sig = self._multi_sig(ent)  # computed ONCE per parameter and step (this runs on the autograd thread, with the GPU waiting behind it)
-        if sig is None:
-            if self.hold:
-                self.ready.append(ent)
-            else:
-                self._launch([ent], None)
-            return
-        lst = self.waiting.setdefault(sig, [])
-        lst.append(ent)
-        if len(lst) >= 8 and not self.hold:
-            self._launch(self.waiting.pop(sig), sig)
-
-    @staticmethod
-    def _multi_sig(ent):
-        """Signature under which complete parameters can share one vmg_conv_wgrad3_multi / vmg_linear_wgrad2_multi launch, or None."""
-        weight, _, entries = ent
-        e0 = entries[0]
-        ks = e0[3]
-        if len(e0[1]) != 1 or ks not in (1, 3) or weight.shape[1] != e0[1][0] or (ks == 3 and weight.dim() != 4):
-            return None
-        if any(e[8] for e in entries) or e0[2].shape[-1] != weight.shape[0]:
-            return None  # (groups of a grouped convolution: the general batched kernel, per output-row range)
-        x0, d0 = e0[0][0], e0[2]
-        if x0.shape[-1] != e0[1][0] or not K.conv_wgrad3_multi_ok(x0, d0, ks):
-            return None
-        xs0, ds0, xt0, dt0, c0, m0 = x0.shape, d0.shape, x0.stride(), d0.stride(), e0[1], e0[3:8]
-        for e in entries[1:]:
-            x, d = e[0][0], e[2]
-            if e[1] != c0 or e[3:8] != m0 or x.shape != xs0 or d.shape != ds0 or x.stride() != xt0 or d.stride() != dt0 or not K.conv_wgrad3_multi_ok(x, d, ks):
-                return None
-        return (tuple(weight.shape), len(entries), e0[1], e0[4], e0[5], e0[6], tuple(xt0), tuple(dt0), ks)
-
-    def _launch(self, ents, sig):
-        """The gradients of the complete parameters `ents`: one by one (sig None or a single parameter) or eight per launch."""
-        for weight, bias, _ in ents:
-            if weight.grad is None:
-                weight.grad = torch.zeros_like(weight, dtype=torch.float32)
-            if bias is not None and bias.requires_grad and bias.grad is None:
-                bias.grad = torch.zeros_like(bias, dtype=torch.float32)
-        if sig is None or len(ents) < 2:
-            for weight, bias, entries in ents:
-                _wgrad_entries(entries, weight.grad, bias.grad if (bias is not None and bias.requires_grad) else None)
-        else:
-            probs = [([e[0][0] for e in entries], [e[2] for e in entries], weight.grad,
-                      bias.grad if (bias is not None and bias.requires_grad) else None, entries[0][7]) for weight, bias, entries in ents]
-            if sig[8] == 3:
-                K.conv_wgrad3_multi(probs, sig[3], sig[4], sig[5])
-            else:
-                K.linear_wgrad2_multi(probs, sig[3] * sig[4] * sig[5])
-        for weight, bias, _ in ents:
-            for cb in self.callbacks:
-                cb(weight)
-            if bias is not None and bias.requires_grad:
-                self._complete(bias)
-
-    def drain(self):
-        """Launch everything that is complete: parameters of one shape share launches (eight per launch).  Between drains (a residual
-        chain completing, the end of the backward pass) shapes that can share a launch wait in `waiting` until eight of them are complete
-        -- the two 3x3 convs of every RCAB, one per TAB, cost three launches per step instead of 24."""
-        if self.ready:
-            ready, self.ready = self.ready, []
-            self._launch(ready, None)
-        if self.waiting:
-            waiting, self.waiting = self.waiting, {}
-            for sig, ents in waiting.items():
-                self._launch(ents, sig)
-
-    def flush_all(self):
-        self._end_of_backward()
-        self.uses.clear()
-
-
-def _wgrad_entries(entries, dW, db):
-    """dW (+= ) the weight gradient of every recorded (sources, src_ch, dpre, ks, N, H, W, scale) entry, batched by shape."""
-    groups = {}
-    for e in entries:
-        sig = (e[1], e[3], e[4], e[5], e[6], e[2].dtype, tuple(e[2].shape[-1:]), e[7], e[8] if len(e) > 8 else 0)
-        groups.setdefault(sig, []).append(e)
-    for (src_ch, ks, N, H, W, _, _, scale, o0), es in groups.items():
-        off = 0
-        for i, c in enumerate(src_ch):
-            xs = [e[0][i][..., :c] if e[0][i].shape[-1] != c else e[0][i] for e in es]
-            K.conv_wgrad_batched(xs, [e[2] for e in es], dW, db if i == 0 else None, ks, N, H, W, scale=scale, i0=off, o0=o0)
-            off += c
-
-
-def _wgrad_now(weight, bias_needed: bool, srcs, src_ch, dpre, ks, N, H, W, scale: float = 1.0):
-    """(dW, db) of one use, as fresh fp32 tensors (mode 'autograd')."""
-    dW = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
-    db = torch.zeros(weight.shape[0], dtype=torch.float32, device=weight.device) if bias_needed else None
-    _wgrad_entries([(srcs, tuple(src_ch), dpre, ks, N, H, W, float(scale), 0)], dW, db)
-    return dW, db
-
-
-DEFERRED = _DeferredWgrad()
-
-
-def set_wgrad_mode(mode: str):
-    """'autograd' (default; weight gradients flow through autograd, DDP-compatible) or 'deferred' (batched per parameter,
-    written straight into .grad; the mode of vmg_amd.train.TrainStep / GradBucketReducer)."""
-    if mode not in ("autograd", "deferred"):
-        raise HipError(f"wgrad mode {mode!r}: 'autograd' or 'deferred'")
-    if mode != DEFERRED.mode:
-        DEFERRED.flush_all()
-        DEFERRED.managed.clear()
-        DEFERRED.mode = mode
-
-
-def flush_deferred_wgrads():
-    """Completes every pending deferred gradient now (the end-of-backward callback does this by itself; kept for callers
-    that read .grad from inside a backward hook)."""
-    DEFERRED.flush_all()
-
-
 def _act_grad(dy: torch.Tensor, y: Optional[torch.Tensor], pre: Optional[torch.Tensor], act: int, slope: float, alpha: float):
     """d(out)/d(pre) applied to dy for out = act(pre) * alpha."""
     if act == hip.ACT_NONE:
@@ -608,8 +334,7 @@ class _Conv2d(_Fn):
         ctx.res_shape = tuple(res.shape) if res is not None else None
         ctx.has_res = res is not None
         ctx.has_bias = bias is not None
-        ctx.defer = DEFERRED.mode == "deferred" and isinstance(weight, torch.nn.Parameter) and ctx.needs_input_grad[0] and \
-            (bias is None or isinstance(bias, torch.nn.Parameter))
+        ctx.defer = DEFERRED.defers(weight, bias, ctx.needs_input_grad[0])
         if ctx.defer:
             ctx.gen = DEFERRED.note_use(weight, bias)
             ctx.bias_ref = bias
@@ -722,47 +447,32 @@ class _GroupedConv2d(_Fn):
         # (measured, tools/bench_grouped_conv.py, forward + backward: 412 -> 305 us at 7 x 64^2 x 112 ch, 334 -> 308 at 32^2 x 224, 329 -> 252 at 16^2 x 224,
         #  but 361 -> 416 at 8^2 x 448, where the dense pack streams 4 x the weights for 448 pixels: up to 256 channels only)
         ctx.dense = GROUPED_DENSE and dt == torch.bfloat16 and ks == 3 and (G * cg) % 8 == 0 and O % 8 == 0 and G * cg <= 256
+        need_pre = act == hip.ACT_GELU and any(ctx.needs_input_grad)
         if ctx.dense:
             C = G * cg
             tiles, mt, deep = choose_tiling(M, O, ks, dt, [C])
             pw = packed(weight, dt, "fwd", tiles=tiles, deep=deep, groups=G)
-            need_pre = act == hip.ACT_GELU and any(ctx.needs_input_grad)
             out, pre = K.conv_forward([x.reshape(N, H, W, C)], pw, bias, N, H, W, act=act, slope=slope, want_pre=need_pre, mt=mt, deep=deep)
-            ctx.cfg = cfg
-            ctx.has_bias = bias is not None
-            ctx.defer = DEFERRED.mode == "deferred" and isinstance(weight, torch.nn.Parameter) and ctx.needs_input_grad[1] and \
-                (bias is None or isinstance(bias, torch.nn.Parameter))
-            if ctx.defer:
-                ctx.gen = DEFERRED.note_params(*([weight] + ([bias] if bias is not None else [])))
-                ctx.bias_ref = bias
-            ctx.srcs = None
-            ctx.save_for_backward(weight, out if act in (hip.ACT_RELU, hip.ACT_LRELU) else None, pre, x)
-            return out
-        cgp = _pad_to(cg)
-        if cgp != cg:  # groups whose channel count is no multiple of 8 (112 / 4 = 28): ONE padded copy (N,H,W,G,cgp), group g = a strided channel slice
-            xp = torch.nn.functional.pad(x.reshape(N, H, W, G, cg), (0, cgp - cg))
-            srcs = [xp[..., g, :] for g in range(G)]
+            srcs = None  # (the backward takes the groups' views from the saved x)
         else:
-            xf = x.reshape(N, H, W, G * cg)
-            srcs = [xf[..., g * cg:(g + 1) * cg] for g in range(G)]
-        out = torch.empty((N, H, W, O), dtype=dt, device=x.device)
-        need_pre = act == hip.ACT_GELU and any(ctx.needs_input_grad)
-        pre = torch.empty_like(out) if need_pre else None
-        tiles, mt, deep = choose_tiling(M, og, ks, dt, [cgp])
-        for g in range(G):
-            pw = packed(weight, dt, "fwd", [cg], tiles=tiles, deep=deep, orange=(g * og, og))
-            K.conv_forward([srcs[g]], pw, None if bias is None else bias[g * og:(g + 1) * og], N, H, W, act=act, slope=slope,
-                           out=out[..., g * og:(g + 1) * og], out_pre=None if pre is None else pre[..., g * og:(g + 1) * og], mt=mt, deep=deep)
+            # groups whose channel count is no multiple of 8 (112 / 4 = 28): ONE padded copy (N,H,W,G,cgp), group g = a strided channel slice
+            srcs = _GroupedConv2d._group_sources(x, N, H, W, G, cg)
+            out = torch.empty((N, H, W, O), dtype=dt, device=x.device)
+            pre = torch.empty_like(out) if need_pre else None
+            tiles, mt, deep = choose_tiling(M, og, ks, dt, [_pad_to(cg)])
+            for g in range(G):
+                pw = packed(weight, dt, "fwd", [cg], tiles=tiles, deep=deep, orange=(g * og, og))
+                K.conv_forward([srcs[g]], pw, None if bias is None else bias[g * og:(g + 1) * og], N, H, W, act=act, slope=slope,
+                               out=out[..., g * og:(g + 1) * og], out_pre=None if pre is None else pre[..., g * og:(g + 1) * og], mt=mt, deep=deep)
         ctx.cfg = cfg
         ctx.has_bias = bias is not None
-        ctx.defer = DEFERRED.mode == "deferred" and isinstance(weight, torch.nn.Parameter) and ctx.needs_input_grad[1] and \
-            (bias is None or isinstance(bias, torch.nn.Parameter))
+        ctx.defer = DEFERRED.defers(weight, bias, ctx.needs_input_grad[1])
         if ctx.defer:
             # one use; its gradient is written straight into .grad by ONE launch over the G groups in the backward (note_params / written)
-            ctx.gen = DEFERRED.note_params(*([weight] + ([bias] if bias is not None else [])))
-            ctx.bias_ref = bias
+            ctx.params = (weight,) if bias is None else (weight, bias)
+            ctx.gen = DEFERRED.note_params(*ctx.params)
         ctx.srcs = srcs  # (views of x / of its padded copy: kept for the weight gradient)
-        ctx.save_for_backward(weight, out if act in (hip.ACT_RELU, hip.ACT_LRELU) else None, pre, None)
+        ctx.save_for_backward(weight, out if act in (hip.ACT_RELU, hip.ACT_LRELU) else None, pre, x if ctx.dense else None)
         return out
 
     @staticmethod
@@ -786,24 +496,25 @@ class _GroupedConv2d(_Fn):
                 pw = packed(weight, dt, "dgrad", None, 0, cg, tiles=tiles, deep=deep, orange=(g * og, og))
                 K.conv_forward([dpre[..., g * og:(g + 1) * og]], pw, None, N, H, W, out=dx[..., g * cg:(g + 1) * cg], mt=mt, deep=deep)
         d_w = d_b = None
-        if ctx.defer:
-            bias = ctx.bias_ref
-            dW = DEFERRED.grad_of(weight)
-            db = DEFERRED.grad_of(bias) if (bias is not None and bias.requires_grad) else None
-            dys = [dpre[..., g * og:(g + 1) * og] for g in range(G)]
-            if ks == 3 and all(K.conv_wgrad3_multi_ok(srcs[g], dys[g], 3) for g in range(G)):
-                # the G groups are G problems of one shape: ONE launch (and one ordered reduce) instead of G of each -- a group's gradient is a
-                # contiguous row slice of the parameter's gradient
-                probs = [([srcs[g][..., :cg] if srcs[g].shape[-1] != cg else srcs[g]], [dys[g]], dW[g * og:(g + 1) * og],
-                          None if db is None else db[g * og:(g + 1) * og], 1.0) for g in range(G)]
-                K.conv_wgrad3_multi(probs, N, H, W)
+        if ctx.needs_input_grad[1]:
+            uses = [recorded([srcs[g]], (cg,), dpre[..., g * og:(g + 1) * og], ks, N, H, W, o0=g * og) for g in range(G)]
+            if ctx.defer:
+                bias = ctx.params[1] if ctx.has_bias else None
+                dW = DEFERRED.grad_of(weight)
+                db = DEFERRED.grad_of(bias) if (bias is not None and bias.requires_grad) else None
+                if ks == 3 and all(K.conv_wgrad3_multi_ok(u.srcs[0], u.dpre, 3) for u in uses):
+                    # the G groups are G problems of one shape: ONE launch (and one ordered reduce) instead of G of each -- a group's gradient is a
+                    # contiguous row slice of the parameter's gradient
+                    probs = [([u.srcs[0][..., :cg] if u.srcs[0].shape[-1] != cg else u.srcs[0]], [u.dpre], dW[u.o0:u.o0 + og],
+                              None if db is None else db[u.o0:u.o0 + og], 1.0) for u in uses]
+                    K.conv_wgrad3_multi(probs, N, H, W)
+                else:
+                    _wgrad_entries(uses, dW, db)
+                DEFERRED.written(ctx.gen, *ctx.params)
             else:
-                _wgrad_entries([([srcs[g]], (cg,), dys[g], ks, N, H, W, 1.0, g * og) for g in range(G)], dW, db)
-            DEFERRED.written(ctx.gen, *([weight] + ([bias] if bias is not None else [])))
-        elif ctx.needs_input_grad[1]:
-            d_w = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
-            d_b = torch.zeros(O, dtype=torch.float32, device=weight.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
-            _wgrad_entries([([srcs[g]], (cg,), dpre[..., g * og:(g + 1) * og], ks, N, H, W, 1.0, g * og) for g in range(G)], d_w, d_b)
+                d_w = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
+                d_b = torch.zeros(O, dtype=torch.float32, device=weight.device) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
+                _wgrad_entries(uses, d_w, d_b)
         elif ctx.has_bias and ctx.needs_input_grad[2]:
             d_b = dpre.float().reshape(-1, O).sum(0)
         return (dx.reshape(ctx.x_shape) if dx is not None else None), d_w, d_b, None
@@ -938,36 +649,33 @@ class _ResidualChain(_Fn):
         pd1 = [packed(params[2 + 4 * k], dt, "dgrad", None, 0, C, tiles=tiles, deep=deep) for k in range(nblk)]
         pd2 = [packed(params[4 + 4 * k], dt, "dgrad", None, 0, C, tiles=tiles, deep=deep) for k in range(nblk)]
         gys, gts = K.resblock_chain_backward(g, ts, pd1, pd2, r, deep)
-        if ctx.defer:
-            DEFERRED.hold += 1  # the chain's parameters complete together: their gradients share launches (drained below)
-        for k in range(nblk - 1, -1, -1):
-            w1, b1, w2, b2 = params[2 + 4 * k: 6 + 4 * k]
+        # the chain's parameters complete together: their gradients share launches (drained when the block is left)
+        with DEFERRED.collecting() if ctx.defer else contextlib.nullcontext():
+            for k in range(nblk - 1, -1, -1):
+                w1, b1, w2, b2 = params[2 + 4 * k: 6 + 4 * k]
+                if ctx.defer:
+                    DEFERRED.add(w2, b2, [ts[k]], [C], gys[k + 1], 3, N, H, W, scale=r, gen=ctx.gen)
+                    DEFERRED.add(w1, b1, [ys[k]], [C], gts[k], 3, N, H, W, gen=ctx.gen)
+                elif ctx.wgrad:
+                    pg[4 + 4 * k], pg[5 + 4 * k] = _wgrad_now(w2, True, [ts[k]], [C], gys[k + 1], 3, N, H, W, scale=r)
+                    pg[2 + 4 * k], pg[3 + 4 * k] = _wgrad_now(w1, True, [ys[k]], [C], gts[k], 3, N, H, W)
+            g = gys[0]
+            w0, b0 = params[0], params[1]
+            dpre0 = K.act_backward(g, y0, hip.ACT_LRELU, 0.1, 1.0)
+            d_srcs = []
+            off = 0
+            for i, c in enumerate(src_ch):
+                if ctx.needs_input_grad[3 + i]:
+                    t_, m_, d_ = choose_tiling(M, c, 3, dt, [C])
+                    dx, _ = K.conv_forward([dpre0], packed(w0, dt, "dgrad", None, off, c, tiles=t_, deep=d_), None, N, H, W, mt=m_, deep=d_)
+                    d_srcs.append(dx)
+                else:
+                    d_srcs.append(None)
+                off += c
             if ctx.defer:
-                DEFERRED.add(w2, b2, [ts[k]], [C], gys[k + 1], 3, N, H, W, scale=r, gen=ctx.gen)
-                DEFERRED.add(w1, b1, [ys[k]], [C], gts[k], 3, N, H, W, gen=ctx.gen)
+                DEFERRED.add(w0, b0, srcs, src_ch, dpre0, 3, N, H, W, gen=ctx.gen)
             elif ctx.wgrad:
-                pg[4 + 4 * k], pg[5 + 4 * k] = _wgrad_now(w2, True, [ts[k]], [C], gys[k + 1], 3, N, H, W, scale=r)
-                pg[2 + 4 * k], pg[3 + 4 * k] = _wgrad_now(w1, True, [ys[k]], [C], gts[k], 3, N, H, W)
-        g = gys[0]
-        w0, b0 = params[0], params[1]
-        dpre0 = K.act_backward(g, y0, hip.ACT_LRELU, 0.1, 1.0)
-        d_srcs = []
-        off = 0
-        for i, c in enumerate(src_ch):
-            if ctx.needs_input_grad[3 + i]:
-                t_, m_, d_ = choose_tiling(M, c, 3, dt, [C])
-                dx, _ = K.conv_forward([dpre0], packed(w0, dt, "dgrad", None, off, c, tiles=t_, deep=d_), None, N, H, W, mt=m_, deep=d_)
-                d_srcs.append(dx)
-            else:
-                d_srcs.append(None)
-            off += c
-        if ctx.defer:
-            DEFERRED.add(w0, b0, srcs, src_ch, dpre0, 3, N, H, W, gen=ctx.gen)
-            DEFERRED.hold -= 1
-            if not DEFERRED.hold:
-                DEFERRED.drain()
-        elif ctx.wgrad:
-            pg[0], pg[1] = _wgrad_now(w0, True, srcs, src_ch, dpre0, 3, N, H, W)
+                pg[0], pg[1] = _wgrad_now(w0, True, srcs, src_ch, dpre0, 3, N, H, W)
         return (None, None, None, *d_srcs, *pg)
 
 
@@ -1256,8 +964,7 @@ class _MorphLinear(_Fn):
         y, tok = K.morphfc_forward(x, axis, chunk, Cp, packed(weight, x.dtype, "fwd", [Cp], tiles=nct), bias, True, 1.0, 1.0 / Cp, want_tokens=ctx.tok_mode)
         ctx.cfg = (axis, chunk, Cp)
         ctx.has_bias = bias is not None
-        ctx.defer = DEFERRED.mode == "deferred" and isinstance(weight, torch.nn.Parameter) and ctx.needs_input_grad[1] and \
-            (bias is None or isinstance(bias, torch.nn.Parameter))
+        ctx.defer = DEFERRED.defers(weight, bias, ctx.needs_input_grad[1])
         if ctx.defer:
             ctx.gen = DEFERRED.note_use(weight, bias)
             ctx.bias_ref = bias

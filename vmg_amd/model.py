@@ -840,7 +840,7 @@ class VMG(nn.Module):
                 m._t1_done = True
         self._forward_calls += 1
         if torch.is_grad_enabled():
-            FH.DEFERRED.begin_forward()  # per-pass use counts of the deferred weight gradients (functional._DeferredWgrad)
+            FH.DEFERRED.begin_forward()  # per-pass use counts of the deferred weight gradients (wgrad._DeferredWgrad)
         # the kernels take fp32 / the module's compute dtype; an enclosing torch.autocast (tools/Trainer.py:132-143) must not
         # re-type the few torch ops left in here
         with torch.autocast("cuda", enabled=False):

@@ -16,6 +16,8 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
+from .wgrad import DEFERRED
+
 
 # ---------------------------------------------------------------------------------------------------------
 # loss (utils/loss.py)
@@ -234,11 +236,8 @@ class GradBucketReducer:
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_autograd) for p in self.params]
         self._order_log: List[torch.nn.Parameter] = []
         self._relaid = optimizer is None  # nothing to re-lay out without a flat optimizer
-        try:  # conv / linear weights are completed by the deferred batched weight-gradient, not by autograd accumulation
-            from . import functional as FH
-            FH.DEFERRED.callbacks[:] = [self._on_grad]  # one reducer per process
-        except Exception:  # pragma: no cover
-            pass
+        # conv / linear weights are completed by the deferred batched weight-gradient, not by autograd accumulation
+        DEFERRED.callbacks[:] = [self._on_grad]  # one reducer per process
         if flat_grad is not None:
             order = [p for _, p in sorted(zip(offsets, self.params), key=lambda t: -t[0])]  # reverse layout order
         else:
@@ -301,14 +300,9 @@ class GradBucketReducer:
 
     def _on_autograd(self, p: torch.nn.Parameter):
         """autograd's post-accumulate hook.  It also fires when a backward node returned NO gradient for the parameter (the deferred
-        batched weight gradients do): such parameters are complete only when functional.DEFERRED says so (its callback)."""
-        try:
-            from . import functional as FH
-            if id(p) in FH.DEFERRED.managed:
-                return
-        except Exception:  # pragma: no cover
-            pass
-        self._on_grad(p)
+        batched weight gradients do): such parameters are complete only when wgrad.DEFERRED says so (its callback)."""
+        if id(p) not in DEFERRED.managed:
+            self._on_grad(p)
 
     def _on_grad(self, p: torch.nn.Parameter):
         if not self.enabled or p not in self.bucket_of or id(p) in self._seen:
