@@ -616,6 +616,34 @@ int vmg_charbonnier_edge_fwd(const float* x, const float* y, float* a1, float* l
 int vmg_charbonnier_edge_bwd(const float* x, const float* y, const float* ld, float* u, float* dx, int64_t planes, int H, int W, float eps,
                              float gs1, float gs2, void* stream);
 
+/* ---- best window per frame, streamed (reference: Tester.test_clips_max, tools/Tester.py:180-213, with psnr_exceed_check :24-34 and
+ * skimage's peak_signal_noise_ratio on [0, 1]-clamped float images) -----------------------------------------------------------------
+ * vmg_frame_sqerr: err[f] = mean over the C*h*w elements of frame f of (clamp(out, 0, 1) - clamp(hr, 0, 1))^2, float64, for n frames.
+ *   out      planar (C, h, w) frames of out_dtype (0 fp32, 1 bf16), frame f at out + f * out_fs ELEMENTS; widened to fp32, clamped in fp32
+ *            (a NaN stays one), subtracted in float64.
+ *   hr       hr_type VMG_HR_F32 / VMG_HR_BF16: planar frames treated like out; VMG_HR_U8: interleaved (h, w, 3) bytes (C must be 3), read in
+ *            place as the correctly rounded fp32 quotient byte / 255 (numpy's astype(float32) / 255.).  Frame f at hr + f * hr_fs elements,
+ *            so a window of a longer clip is read where it lies.
+ *   ws       vmg_frame_sqerr_ws_bytes(n, C, h, w) bytes, 8-byte aligned: one float64 partial per workgroup.  The number of workgroups per
+ *            frame depends on the frame size alone; a second launch adds each frame's partials in index order.  No atomics: two calls on the
+ *            same input give the same bits.
+ * vmg_best_window_select: one window's n frames (frames t0 .. t0 + n - 1 of the T of the sequence) against the running best.  Per frame
+ *   psnr = (float)(err == 0 ? cap : 10 * log10(1 / err)); if window == 0 or psnr > best_in[t] (strictly) the frame is copied into
+ *   canvas + t * frame_elems as fp32 and best_out[t] = psnr, choice_out[t] = window; otherwise, and for every frame outside the window,
+ *   best_out[t] = best_in[t] and choice_out[t] = choice_in[t].  With best_in = 0 and a zero canvas in front of window 0 this is torch.max's
+ *   first maximum over the reference's score table, whose uncovered entries are 0.  best / choice are ping-ponged: *_in and *_out (T
+ *   entries each) must differ.  table: null, or (T, n_windows) fp32 that receives psnr at [t][window] for the covered frames.
+ *   16-byte vector copies where a frame and its canvas slot reach a 16-byte boundary at the same element, single elements elsewhere. */
+#define VMG_HR_F32 0
+#define VMG_HR_BF16 1
+#define VMG_HR_U8 2
+int64_t vmg_frame_sqerr_ws_bytes(int n, int C, int h, int w);
+int vmg_frame_sqerr(int out_dtype, const void* out, int64_t out_fs, int hr_type, const void* hr, int64_t hr_fs, int n, int C, int h, int w,
+                    void* ws, int64_t ws_bytes, double* err, void* stream);
+int vmg_best_window_select(int dtype, const void* out, int64_t out_fs, const double* err, int n, int64_t frame_elems, int T, int t0, int window,
+                           float cap, float* canvas, const float* best_in, const int* choice_in, float* best_out, int* choice_out,
+                           float* table, int n_windows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,10 @@ SIGNATURES = {
     "vmg_prof_end": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int), POINTER(ctypes.c_double)]),
     "vmg_conv_wgrad": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,
                                c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p]),
+    "vmg_frame_sqerr_ws_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "vmg_frame_sqerr": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "vmg_best_window_select": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 

@@ -371,6 +371,115 @@ def test_clips_max(model: Callable, inputs: torch.Tensor, HR: torch.Tensor, num_
     return torch.gather(E, dim=2, index=max_idx).squeeze().to(inputs.dtype)
 
 
+PSNR_CAP = float(10 * np.log10(255.0 ** 2 / 0.65025))  # psnr_exceed_check's replacement of an infinite score (tools/Tester.py:24-34)
+
+
+@torch.no_grad()
+def best_window_clips(model: Callable, inputs: torch.Tensor, HR: torch.Tensor, num_frames: int, overlap_frames: int,
+                      test_spatial: Optional[Sequence[int]] = None, overlap_spatial: Optional[int] = None, scale: int = 4, return_scores: bool = False):
+    """test_clips_max streamed: the same windows in the same order and the same frames out, (T, C, 4H, 4W) in inputs.dtype, but one window
+    at a time.  Per window: the network, one vmg_frame_sqerr call (float64 error of every frame against HR), one vmg_best_window_select call
+    (float32 score, "first maximum wins", copy of the winning frames).  No score visits the host and nothing is synchronised; the function owns
+    one (T, C, 4H, 4W) fp32 canvas, two (T,) float32 and two (T,) int32 arrays and the reduction workspace.
+    HR: (1, T, 3, 4H, 4W) fp32 / bf16, or (T, 4H, 4W, 3) uint8, scored in place as byte / 255 (Tester.evaluate's HR.astype(np.float32) / 255.).
+    return_scores: also (choice (T,) int32, best (T,) float32, table (T, n_windows) float32 with 0 where a window does not cover a frame),
+    all on the device."""
+    from . import kernels as K
+    hip.require_cuda(inputs, HR)
+    B, T, C, H, W = inputs.shape
+    if B != 1:
+        raise ValueError(f"best_window_clips: one sequence at a time (the reference's selection is defined for a batch of one), got B = {B}")
+    hh, ww = H * scale, W * scale
+    if HR.dtype == torch.uint8:
+        if tuple(HR.shape) != (T, hh, ww, 3) or C != 3:
+            raise ValueError(f"best_window_clips: uint8 HR must be (T, 4H, 4W, 3) = {(T, hh, ww, 3)}, got {tuple(HR.shape)}")
+        hr = HR
+    else:
+        if tuple(HR.shape) != (1, T, C, hh, ww):
+            raise ValueError(f"best_window_clips: float HR must be (1, T, C, 4H, 4W) = {(1, T, C, hh, ww)}, got {tuple(HR.shape)}")
+        hr = HR[0]
+    if not hr[0].is_contiguous():
+        hr = hr.contiguous()
+    ts = tile_starts(T, num_frames, overlap_frames)
+    if ts[-1] + num_frames > T:
+        raise ValueError(f"best_window_clips: windows of {num_frames} frames do not fit {T} frames")
+    dev = inputs.device
+    canvas = torch.zeros(T, C, hh, ww, dtype=torch.float32, device=dev)
+    best = torch.zeros(2, T, dtype=torch.float32, device=dev)
+    choice = torch.zeros(2, T, dtype=torch.int32, device=dev)
+    table = torch.zeros(T, len(ts), dtype=torch.float32, device=dev) if return_scores else None
+    ws = torch.empty(max(K.frame_sqerr_ws_bytes(num_frames, C, hh, ww), 8), dtype=torch.uint8, device=dev)
+    err = torch.empty(num_frames, dtype=torch.float64, device=dev)
+    for idx, t in enumerate(ts):
+        clip = inputs[:, t:t + num_frames]
+        out = model(clip) if overlap_spatial is None else test_image(model, clip, test_spatial, overlap_spatial, scale)
+        if tuple(out.shape) != (1, num_frames, C, hh, ww):
+            raise ValueError(f"best_window_clips: the network returned {tuple(out.shape)} for window {idx}, expected {(1, num_frames, C, hh, ww)}")
+        o = out[0]
+        if o.dtype not in (torch.float32, torch.bfloat16):
+            o = o.float()
+        if not o[0].is_contiguous():
+            o = o.contiguous()
+        cur, nxt = idx & 1, (idx + 1) & 1
+        K.frame_sqerr(o, hr[t:t + num_frames], ws, err)
+        K.best_window_select(o, err, t, idx, PSNR_CAP, canvas, best[cur], choice[cur], best[nxt], choice[nxt], table)
+    frames = canvas.to(inputs.dtype)
+    if return_scores:
+        last = len(ts) & 1
+        return frames, (choice[last], best[last], table)
+    return frames
+
+
+def _augment(x: torch.Tensor, hflip: bool, vflip: bool, rot90: bool, interleaved: bool = False) -> torch.Tensor:
+    """Tester.augment / augment_inverse (tools/Tester.py:387-445; the two are the same function): flip the width axis, flip the height axis,
+    swap the two, in this order.  Planar (..., H, W) tensors, or interleaved (T, H, W, 3) ones."""
+    ax_h, ax_w = (1, 2) if interleaved else (x.dim() - 2, x.dim() - 1)
+    if hflip:
+        x = x.flip(ax_w)
+    if vflip:
+        x = x.flip(ax_h)
+    if rot90:
+        x = x.transpose(ax_h, ax_w)
+    return x.contiguous()
+
+
+_U8_TO_UNIT = {}
+
+
+def _u8_to_unit(device: torch.device) -> torch.Tensor:
+    """The 256 values of numpy's byte.astype(np.float32) / 255. -- numpy's own quotients, so the bits are the reference's."""
+    lut = _U8_TO_UNIT.get(device)
+    if lut is None:
+        lut = _U8_TO_UNIT[device] = torch.from_numpy(np.arange(256).astype(np.float32) / 255.).to(device)
+    return lut
+
+
+@torch.no_grad()
+def evaluate_reds(model: Callable, lr_u8: torch.Tensor, hr_u8: torch.Tensor, num_frames: int, overlap_frames: int,
+                  test_spatial: Optional[Sequence[int]] = None, overlap_spatial: Optional[int] = None, scale: int = 4, hflip: bool = False,
+                  vflip: bool = False, rot90: bool = False) -> torch.Tensor:
+    """Tester.evaluate for dataset_name == 'REDS' (tools/Tester.py:215-252) from uint8 frames to uint8 frames on the device: lr_u8 (T, H, W, 3)
+    and hr_u8 (T, 4H, 4W, 3) RGB -> (T, 4H, 4W, 3) uint8, the frames metrics.frame_metrics scores.  The LR clip becomes (1, T, 3, H, W) fp32 as
+    byte / 255; HR stays uint8 and is scored where it lies (best_window_clips).
+    hflip / vflip / rot90: the reference's data_enhance.  Tester.augment runs on both clips before the network and Tester.augment_inverse --
+    the same three steps in the same order -- on the output.  A single flag (or all three) is undone by that; exactly one flip together with rot90 comes
+    back rotated by 180 degrees, as the reference's frames do.  With flags on the HR clip is materialised once more, as flipped uint8."""
+    hip.require_cuda(lr_u8, hr_u8)
+    if lr_u8.dtype != torch.uint8 or hr_u8.dtype != torch.uint8 or lr_u8.dim() != 4 or hr_u8.dim() != 4 or lr_u8.shape[3] != 3 or hr_u8.shape[3] != 3:
+        raise ValueError(f"evaluate_reds: uint8 (T, H, W, 3) and (T, 4H, 4W, 3) expected, got {lr_u8.dtype} {tuple(lr_u8.shape)} and "
+                         f"{hr_u8.dtype} {tuple(hr_u8.shape)}")
+    x = _u8_to_unit(lr_u8.device)[lr_u8.permute(0, 3, 1, 2).long()].unsqueeze(0)  # 1, T, 3, H, W
+    hr = hr_u8
+    enhance = hflip or vflip or rot90
+    if enhance:
+        x = _augment(x, hflip, vflip, rot90)
+        hr = _augment(hr, hflip, vflip, rot90, interleaved=True)
+    out = best_window_clips(model, x.contiguous(), hr, num_frames, overlap_frames, test_spatial, overlap_spatial, scale)
+    if enhance:
+        out = _augment(out, hflip, vflip, rot90)
+    return to_uint8_device(out).permute(0, 2, 3, 1)
+
+
 @torch.no_grad()
 def to_uint8_device(outputs: torch.Tensor) -> torch.Tensor:
     """tools/Tester.py:249-250 without the host copy: clamp, *255, round half to even -> torch.uint8 (T, 3, H, W) on the device (the

@@ -1383,3 +1383,71 @@ def crop_batch(frames: torch.Tensor, strides: Sequence[int], desc: torch.Tensor,
     hip.check(hip.lib().vmg_crop_batch(frames.data_ptr(), st, desc.data_ptr(), N, int(H), int(W), int(ch), int(cw), int(bool(channel_reverse)),
                                        CROP_OUT_TYPES[out.dtype], out.data_ptr(), hip.stream_ptr()), "vmg_crop_batch")
     return out
+
+
+HR_TYPES = {torch.float32: 0, torch.bfloat16: 1, torch.uint8: 2}  # VMG_HR_* of include/vmg_hip.h
+
+
+def _frame_stride(t: torch.Tensor, what: str) -> int:
+    """Element stride between the frames of a (n, ...) VIEW whose frames are dense runs (a window cut from a longer clip is one)."""
+    if not t[0].is_contiguous():
+        raise HipError(f"{what}: every frame must be a dense run of elements, got strides {tuple(t.stride())} for {tuple(t.shape)}")
+    return int(t.stride(0)) if t.shape[0] > 1 else 0
+
+
+def frame_sqerr_ws_bytes(n: int, C: int, h: int, w: int) -> int:
+    return int(hip.lib().vmg_frame_sqerr_ws_bytes(int(n), int(C), int(h), int(w)))
+
+
+def frame_sqerr(out: torch.Tensor, hr: torch.Tensor, ws: Optional[torch.Tensor] = None, err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vmg_frame_sqerr: err[f] = float64 mean of (clamp(out[f], 0, 1) - clamp(hr[f], 0, 1))^2.  out: (n, C, h, w) fp32 / bf16 view with dense frames;
+    hr: the same shape in fp32 / bf16, or (n, h, w, 3) uint8 read as byte / 255.  ws: at least frame_sqerr_ws_bytes(n, C, h, w) bytes; err: (>= n)
+    float64, the first n entries are written and returned.  Two launches, nothing is synchronised."""
+    hip.require_cuda(out, hr, ws, err)
+    if out.dim() != 4 or out.dtype not in (torch.float32, torch.bfloat16):
+        raise HipError(f"frame_sqerr: out must be (n, C, h, w) fp32 or bf16, got {out.dtype} {tuple(out.shape)}")
+    n, C, h, w = out.shape
+    if hr.dtype not in HR_TYPES:
+        raise HipError(f"frame_sqerr: hr must be fp32, bf16 or uint8, got {hr.dtype}")
+    want = (n, h, w, 3) if hr.dtype == torch.uint8 else (n, C, h, w)
+    if tuple(hr.shape) != want or (hr.dtype == torch.uint8 and C != 3):
+        raise HipError(f"frame_sqerr: hr must be {want} for out {tuple(out.shape)}, got {tuple(hr.shape)}")
+    need = frame_sqerr_ws_bytes(n, C, h, w)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=out.device)
+    if err is None:
+        err = torch.empty(n, dtype=torch.float64, device=out.device)
+    if err.dtype != torch.float64 or not err.is_contiguous() or err.numel() < n:
+        raise HipError("frame_sqerr: err must be a contiguous float64 tensor of at least n entries")
+    if not ws.is_contiguous():
+        raise HipError("frame_sqerr: the workspace must be contiguous")
+    hip.check(hip.lib().vmg_frame_sqerr(hip.dtype_code(out.dtype), out.data_ptr(), _frame_stride(out, "frame_sqerr"), HR_TYPES[hr.dtype], hr.data_ptr(),
+                                        _frame_stride(hr, "frame_sqerr"), n, C, h, w, ws.data_ptr(), ws.numel() * ws.element_size(), err.data_ptr(),
+                                        hip.stream_ptr()), "vmg_frame_sqerr")
+    return err[:n]
+
+
+def best_window_select(out: torch.Tensor, err: torch.Tensor, t0: int, window: int, cap: float, canvas: torch.Tensor, best_in: torch.Tensor,
+                       choice_in: torch.Tensor, best_out: torch.Tensor, choice_out: torch.Tensor, table: Optional[torch.Tensor] = None) -> None:
+    """vmg_best_window_select: the n frames of `out` ((n, C, h, w) fp32 / bf16, dense frames) are frames t0 .. t0 + n - 1 of the (T, C, h, w) fp32
+    canvas.  A frame whose float32 score (from err, `cap` where err == 0) beats best_in strictly -- every frame when window == 0 -- is copied into
+    its slot; best / choice (T fp32 / int32 each) move from *_in to *_out.  table: None or (T, n_windows) fp32.  One launch, no synchronisation."""
+    hip.require_cuda(out, err, canvas, best_in, choice_in, best_out, choice_out, table)
+    if out.dim() != 4 or canvas.dim() != 4 or out.shape[1:] != canvas.shape[1:]:
+        raise HipError(f"best_window_select: frames {tuple(out.shape)} do not fit the canvas {tuple(canvas.shape)}")
+    if canvas.dtype != torch.float32 or not canvas.is_contiguous():
+        raise HipError("best_window_select: the canvas must be contiguous fp32")
+    n, T = out.shape[0], canvas.shape[0]
+    if err.dtype != torch.float64 or not err.is_contiguous() or err.numel() < n:
+        raise HipError("best_window_select: err must be a contiguous float64 tensor of at least n entries")
+    for name, t, dt in (("best_in", best_in, torch.float32), ("best_out", best_out, torch.float32), ("choice_in", choice_in, torch.int32),
+                        ("choice_out", choice_out, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != T:
+            raise HipError(f"best_window_select: {name} must be a contiguous {dt} tensor of {T} entries")
+    if table is not None and (table.dtype != torch.float32 or not table.is_contiguous() or table.dim() != 2 or table.shape[0] != T):
+        raise HipError(f"best_window_select: the table must be a contiguous fp32 ({T}, n_windows) tensor")
+    n_windows = int(table.shape[1]) if table is not None else int(window) + 1
+    hip.check(hip.lib().vmg_best_window_select(hip.dtype_code(out.dtype), out.data_ptr(), _frame_stride(out, "best_window_select"), err.data_ptr(), n,
+                                               out[0].numel(), T, int(t0), int(window), float(cap), canvas.data_ptr(), best_in.data_ptr(),
+                                               choice_in.data_ptr(), best_out.data_ptr(), choice_out.data_ptr(),
+                                               table.data_ptr() if table is not None else None, n_windows, hip.stream_ptr()), "vmg_best_window_select")
