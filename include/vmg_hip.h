@@ -644,6 +644,32 @@ int vmg_best_window_select(int dtype, const void* out, int64_t out_fs, const dou
                            float cap, float* canvas, const float* best_in, const int* choice_in, float* best_out, int* choice_out,
                            float* table, int n_windows, void* stream);
 
+/* ---- frame stacks <-> network clips (reference: Tester.evaluate, tools/Tester.py:215-252, with Tester.augment / augment_inverse :387-445,
+ * which are one function) ------------------------------------------------------------------------------------------------------------
+ * T frames of 3 channels, H x W on the source side, converted and written to the destination in one launch.  Both sides are VIEWS given by
+ * four ELEMENT strides {frame, channel, row, column}: interleaved (T, H, W, 3) frames are {3HW, 1, 3W, 3}, planar ones {3HW, HW, W, 1}; every
+ * second frame or a crop of a larger frame only change the numbers.  Planar (column stride 1) and interleaved (column 3, channel 1) sides
+ * move 16 / 8 / 4-byte vectors wherever four elements of a row start at such a boundary and single elements elsewhere, any other strides
+ * move single elements; no base alignment beyond the element's and no row length is required.
+ * flags = hflip | vflip << 1 | rot90 << 2, Tester.augment's three steps in its order (flip width, flip height, swap the two axes):
+ *   destination (r, c) = source (vflip ? H - 1 - i : i, hflip ? W - 1 - j : j) with (i, j) = rot90 ? (c, r) : (r, c);
+ *   the destination frames are W x H (rows x columns) when rot90 is set, H x W otherwise.
+ * Type pairs (VMG_FRAME_*):
+ *   U8 -> F32   byte / 255 as the correctly rounded fp32 quotient (numpy's astype(np.float32) / 255.)
+ *   U8 -> BF16  that fp32 value rounded to bf16 once (nearest even)
+ *   F32 / BF16 -> U8   (unsigned char)rintf(fminf(fmaxf(x, 0), 1) * 255.0f): clamp, * 255 in fp32, round half to even (tools/Tester.py:249-250).
+ *                      Finite inputs only: the reference's cast of a NaN is undefined.
+ *   U8 -> U8    the bytes themselves
+ * The call refuses, with a message and without a launch: a null pointer, T, H or W < 1 (or H, W > 65536, T > 2^20), flags outside 0..7, any
+ * other type pair, a negative stride, destination strides under which two of its elements coincide, a pointer not aligned to its element,
+ * and source and destination byte ranges that overlap (the conversion does not run in place).  No allocation, no workspace, nothing is
+ * added across threads: equal inputs give equal bits. */
+#define VMG_FRAME_U8 0
+#define VMG_FRAME_F32 1
+#define VMG_FRAME_BF16 2
+int vmg_convert_frames(int src_type, const void* src, const int64_t* src_strides, int dst_type, void* dst, const int64_t* dst_strides, int T, int H,
+                       int W, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

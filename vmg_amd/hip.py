@@ -191,6 +191,7 @@ SIGNATURES = {
     "vmg_frame_sqerr": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "vmg_best_window_select": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vmg_convert_frames": (c_int, [c_int, c_void_p, POINTER(c_int64), c_int, c_void_p, POINTER(c_int64), c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 

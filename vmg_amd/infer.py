@@ -499,3 +499,181 @@ def to_uint8(outputs: torch.Tensor) -> np.ndarray:
     ones = torch.ones_like(o)
     u8 = _finalize(o, ones, want_u8=True)
     return np.ascontiguousarray(u8.cpu().numpy().transpose(0, 2, 3, 1))
+
+
+# ---- Tester.evaluate on the device: uint8 frames in, uint8 frames out (one conversion kernel each way) ----------------------------------
+def _frames_view(frames: torch.Tensor, what: str, dtypes) -> torch.Tensor:
+    """The (T, 3, H, W) view (no copy) of planar (T, 3, H, W) or interleaved (T, H, W, 3) frames, themselves views of any strides.  A length-3
+    axis in front is taken for the channels (as metrics.frame_metrics reads its frames), else the one at the end."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+        raise ValueError(f"{what}: (T, H, W, 3) or (T, 3, H, W) frames expected, got {tuple(frames.shape) if isinstance(frames, torch.Tensor) else type(frames)}")
+    if frames.dtype not in dtypes:
+        raise ValueError(f"{what}: {' / '.join(str(d) for d in dtypes)} expected, got {frames.dtype}")
+    if frames.shape[1] == 3:
+        return frames
+    if frames.shape[3] == 3:
+        return frames.permute(0, 3, 1, 2)
+    raise ValueError(f"{what}: no RGB axis of length 3 in {tuple(frames.shape)}")
+
+
+def _check_out(out: torch.Tensor, shape, dtype, what: str) -> torch.Tensor:
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype:
+        raise ValueError(f"{what}: out must be {dtype} {tuple(shape)}, got {getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))}")
+    return out
+
+
+@torch.no_grad()
+def frames_to_clip(frames_u8: torch.Tensor, dtype: torch.dtype = torch.float32, hflip: bool = False, vflip: bool = False, rot90: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Tester.evaluate's way in (tools/Tester.py:217-221): uint8 (T, H, W, 3) or (T, 3, H, W) frames, or views of them, -> the (1, T, 3, H', W')
+    clip of byte / 255 in `dtype` (fp32: numpy's quotients bit for bit; bf16: those rounded once), Tester.augment applied ((H', W') = (W, H) with
+    rot90).  One launch of vmg_convert_frames; the frames are read where they lie.  out: a (1, T, 3, H', W') tensor of `dtype`, any strides."""
+    from . import kernels as K
+    hip.require_cuda(frames_u8, out)
+    src = _frames_view(frames_u8, "frames_to_clip", (torch.uint8,))
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"frames_to_clip: the clip is float32 or bfloat16, got {dtype}")
+    T, _, H, W = src.shape
+    shape = (1, T, 3, W, H) if rot90 else (1, T, 3, H, W)
+    out = torch.empty(shape, dtype=dtype, device=src.device) if out is None else _check_out(out, shape, dtype, "frames_to_clip")
+    K.convert_frames(src, out[0], hflip, vflip, rot90)
+    return out
+
+
+@torch.no_grad()
+def clip_to_frames(clip: torch.Tensor, hflip: bool = False, vflip: bool = False, rot90: bool = False, planar: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Tester.evaluate's way out (tools/Tester.py:245-250): a (1, T, 3, h, w) or (T, 3, h, w) fp32 / bf16 clip of any strides -> contiguous uint8
+    (T, H', W', 3) frames -- (T, 3, H', W') with planar -- of clamp(0, 1) * 255 rounded half to even, Tester.augment_inverse applied first
+    ((H', W') = (w, h) with rot90).  One launch; the result is the only allocation.  out: uint8 of the result's shape, any strides (a view
+    into a larger buffer is written in place and nothing around it is touched)."""
+    from . import kernels as K
+    hip.require_cuda(clip, out)
+    if not isinstance(clip, torch.Tensor) or clip.dim() not in (4, 5) or (clip.dim() == 5 and clip.shape[0] != 1) or clip.shape[-3] != 3:
+        raise ValueError(f"clip_to_frames: a (1, T, 3, h, w) or (T, 3, h, w) clip expected, got {tuple(getattr(clip, 'shape', ()))}")
+    if clip.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"clip_to_frames: a float32 or bfloat16 clip expected, got {clip.dtype}")
+    src = clip[0] if clip.dim() == 5 else clip
+    T, _, h, w = src.shape
+    hh, ww = (w, h) if rot90 else (h, w)
+    shape = (T, 3, hh, ww) if planar else (T, hh, ww, 3)
+    out = torch.empty(shape, dtype=torch.uint8, device=src.device) if out is None else _check_out(out, shape, torch.uint8, "clip_to_frames")
+    K.convert_frames(src, out if planar else out.permute(0, 3, 1, 2), hflip, vflip, rot90)
+    return out
+
+
+@torch.no_grad()
+def augment_frames(frames_u8: torch.Tensor, hflip: bool, vflip: bool, rot90: bool) -> torch.Tensor:
+    """Tester.augment (== augment_inverse) on uint8 frames, (T, H, W, 3) or (T, 3, H, W) or views of them: contiguous frames of the same layout,
+    one launch."""
+    from . import kernels as K
+    hip.require_cuda(frames_u8)
+    src = _frames_view(frames_u8, "augment_frames", (torch.uint8,))
+    T, _, H, W = src.shape
+    hh, ww = (W, H) if rot90 else (H, W)
+    if frames_u8.shape[1] == 3:
+        out = torch.empty((T, 3, hh, ww), dtype=torch.uint8, device=src.device)
+        K.convert_frames(src, out, hflip, vflip, rot90)
+    else:
+        out = torch.empty((T, hh, ww, 3), dtype=torch.uint8, device=src.device)
+        K.convert_frames(src, out.permute(0, 3, 1, 2), hflip, vflip, rot90)
+    return out
+
+
+@torch.no_grad()
+def evaluate(model: Callable, lr_u8: torch.Tensor, hr_u8: Optional[torch.Tensor] = None, dataset_name: str = "REDS", num_frames: int = 7,
+             overlap_frames: int = 0, test_spatial: Optional[Sequence[int]] = None, overlap_spatial: Optional[int] = None, scale: int = 4,
+             hflip: bool = False, vflip: bool = False, rot90: bool = False) -> torch.Tensor:
+    """Tester.evaluate (tools/Tester.py:215-252) on the device: uint8 RGB frames lr_u8 (T, H, W, 3) -> uint8 (T, 4H, 4W, 3), the frames
+    metrics.frame_metrics scores.  The three branches of the reference, chosen by dataset_name:
+      'Vimeo90k_septuplet'  one network call on the whole clip, or test_image when overlap_spatial is set;
+      'REDS'                best_window_clips against hr_u8 (T, 4H, 4W, 3), which is required (scored in place as byte / 255);
+      any other name        test_clips (Vid4, UDM10, ...).
+    The clip goes in through frames_to_clip (fp32, as the reference feeds the network) and comes out through clip_to_frames, one launch each.
+    hflip / vflip / rot90: the reference's data_enhance, folded into those two launches -- Tester.augment on the way in (and on the HR clip, one
+    more launch, uint8 -> uint8) and augment_inverse, the same three steps in the same order, on the way out.  As in the reference a single
+    flag, both flips, or all three are undone by that; exactly one flip together with rot90 comes back rotated by 180 degrees (see evaluate_reds,
+    whose bytes the REDS branch reproduces)."""
+    hip.require_cuda(lr_u8, hr_u8)
+    if not isinstance(lr_u8, torch.Tensor) or lr_u8.dtype != torch.uint8 or lr_u8.dim() != 4 or lr_u8.shape[3] != 3:
+        raise ValueError(f"evaluate: uint8 (T, H, W, 3) frames expected, got {getattr(lr_u8, 'dtype', None)} {tuple(getattr(lr_u8, 'shape', ()))}")
+    reds = isinstance(dataset_name, str) and dataset_name == "REDS"
+    if reds:
+        T, H, W, _ = lr_u8.shape
+        if hr_u8 is None:
+            raise ValueError("evaluate: the REDS branch picks each frame's window by its PSNR against HR: hr_u8 is required")
+        if hr_u8.dtype != torch.uint8 or tuple(hr_u8.shape) != (T, H * scale, W * scale, 3):
+            raise ValueError(f"evaluate: hr_u8 must be uint8 {(T, H * scale, W * scale, 3)}, got {hr_u8.dtype} {tuple(hr_u8.shape)}")
+    x = frames_to_clip(lr_u8.permute(0, 3, 1, 2), torch.float32, hflip, vflip, rot90)
+    if reds:
+        hr = hr_u8
+        if hflip or vflip or rot90:
+            from . import kernels as K
+            hr = torch.empty((T, W * scale, H * scale, 3) if rot90 else (T, H * scale, W * scale, 3), dtype=torch.uint8, device=hr_u8.device)
+            K.convert_frames(hr_u8.permute(0, 3, 1, 2), hr.permute(0, 3, 1, 2), hflip, vflip, rot90)
+        out = best_window_clips(model, x, hr, num_frames, overlap_frames, test_spatial, overlap_spatial, scale)
+    elif isinstance(dataset_name, str) and dataset_name == "Vimeo90k_septuplet":
+        out = model(x) if overlap_spatial is None else test_image(model, x, test_spatial, overlap_spatial, scale)
+    else:
+        out = test_clips(model, x, num_frames, overlap_frames, test_spatial, overlap_spatial, scale)
+    if out.dtype not in (torch.float32, torch.bfloat16):
+        out = out.float()
+    return clip_to_frames(out, hflip, vflip, rot90)
+
+
+def index_generation(num_output_frames: int, num_GT: int) -> List[List[int]]:
+    """utils/eval_utils.py:38-61: the index lists a sequence of num_GT frames is evaluated in -- runs of num_output_frames frames that share
+    one frame with their predecessor, plus one flush with the end when the last frame is not reached.  Host logic."""
+    indices_list = []
+    right = num_output_frames
+    while right <= num_GT:
+        indices_list.append(list(range(right - num_output_frames, right)))
+        right += num_output_frames - 1
+    if right - num_output_frames < num_GT - 1:
+        indices_list.append(list(range(num_GT - num_output_frames, num_GT)))
+    return indices_list
+
+
+def _runs(positions: Sequence[int]) -> List[Tuple[int, int]]:
+    """[lo, hi) runs of consecutive integers in an ascending list."""
+    runs: List[Tuple[int, int]] = []
+    for p in positions:
+        if runs and runs[-1][1] == p:
+            runs[-1] = (runs[-1][0], p + 1)
+        else:
+            runs.append((p, p + 1))
+    return runs
+
+
+@torch.no_grad()
+def evaluate_sequence(model: Callable, lr_u8: torch.Tensor, gt_u8: torch.Tensor, num_out_frames: int, board, **evaluate_kwargs) -> torch.Tensor:
+    """The per-sequence body of tools/test_reds4.py:155-250 between board.start_sequence(...) and board.end_sequence(), which stay with the
+    caller: for every index list of index_generation(num_out_frames, N) the frames lr_u8[indices] (N, H, W, 3) go through evaluate (with
+    gt_u8[indices] as HR on the REDS branch); the frames of the list that no earlier list has scored are scored against gt_u8 (N, 4H, 4W, 3) by
+    metrics.frame_metrics and handed to board.add_clip, which keeps the reference's eval_mid_clip / use_mirrors positions.  Returns the
+    (N, 4H, 4W, 3) uint8 frames, each as the first list that reached it produced it (the frames the reference writes to disk).  The host is
+    synchronised only where frame_metrics reads its sums back, once per scored run of frames."""
+    from . import metrics as M
+    hip.require_cuda(lr_u8, gt_u8)
+    if lr_u8.dim() != 4 or gt_u8.dim() != 4 or lr_u8.shape[0] != gt_u8.shape[0]:
+        raise ValueError(f"evaluate_sequence: (N, H, W, 3) and (N, 4H, 4W, 3) frames expected, got {tuple(lr_u8.shape)} and {tuple(gt_u8.shape)}")
+    N = lr_u8.shape[0]
+    if not 1 <= int(num_out_frames) <= N:
+        raise ValueError(f"evaluate_sequence: index lists of {num_out_frames} frames do not fit a sequence of {N}")
+    reds = evaluate_kwargs.get("dataset_name", "REDS") == "REDS"
+    frames = torch.empty_like(gt_u8, memory_format=torch.contiguous_format)
+    scored = set()
+    nan = float("nan")
+    for indices in index_generation(int(num_out_frames), N):
+        lo, hi = indices[0], indices[-1] + 1  # (an index list is a run of consecutive frames: a view, not a gather)
+        out = evaluate(model, lr_u8[lo:hi], gt_u8[lo:hi] if reds else None, **evaluate_kwargs)
+        new = [pos for pos, fr in enumerate(indices) if fr not in scored]
+        cols = [[nan] * len(indices) for _ in M.METRICS]  # (add_clip skips the positions scored before; their slots are never read)
+        for p0, p1 in _runs(new):
+            frames[lo + p0:lo + p1].copy_(out[p0:p1])
+            vals = M.frame_metrics(out[p0:p1], gt_u8[lo + p0:lo + p1])
+            for col, v in zip(cols, vals):
+                col[p0:p1] = v.tolist()
+        scored.update(indices)
+        board.add_clip(indices, cols)
+    return frames

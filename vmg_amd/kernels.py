@@ -1451,3 +1451,26 @@ def best_window_select(out: torch.Tensor, err: torch.Tensor, t0: int, window: in
                                                out[0].numel(), T, int(t0), int(window), float(cap), canvas.data_ptr(), best_in.data_ptr(),
                                                choice_in.data_ptr(), best_out.data_ptr(), choice_out.data_ptr(),
                                                table.data_ptr() if table is not None else None, n_windows, hip.stream_ptr()), "vmg_best_window_select")
+
+
+FRAME_TYPES = {torch.uint8: 0, torch.float32: 1, torch.bfloat16: 2}  # VMG_FRAME_* of include/vmg_hip.h
+
+
+def convert_frames(src: torch.Tensor, dst: torch.Tensor, hflip: bool = False, vflip: bool = False, rot90: bool = False) -> torch.Tensor:
+    """vmg_convert_frames on two (T, 3, h, w) VIEWS of any strides (planar or interleaved storage, frame subsets, crops): dst = Tester.augment
+    of src (flip width, flip height, swap the axes) converted uint8 -> fp32 / bf16 (byte / 255), fp32 / bf16 -> uint8 (clamp, * 255, round
+    half to even) or uint8 -> uint8.  dst is (T, 3, w, h) with rot90.  One launch, no workspace, nothing is synchronised."""
+    hip.require_cuda(src, dst)
+    if src.dtype not in FRAME_TYPES or dst.dtype not in FRAME_TYPES:
+        raise HipError(f"convert_frames: uint8, float32 and bfloat16 are the element types, got {src.dtype} -> {dst.dtype}")
+    if src.dim() != 4 or src.shape[1] != 3:
+        raise HipError(f"convert_frames: a (T, 3, H, W) source view expected, got {tuple(src.shape)}")
+    T, _, H, W = src.shape
+    want = (T, 3, W, H) if rot90 else (T, 3, H, W)
+    if tuple(dst.shape) != want:
+        raise HipError(f"convert_frames: the destination view must be {want}, got {tuple(dst.shape)}")
+    flags = int(bool(hflip)) | int(bool(vflip)) << 1 | int(bool(rot90)) << 2
+    ss, ds = (ctypes.c_int64 * 4)(*src.stride()), (ctypes.c_int64 * 4)(*dst.stride())
+    hip.check(hip.lib().vmg_convert_frames(FRAME_TYPES[src.dtype], src.data_ptr(), ss, FRAME_TYPES[dst.dtype], dst.data_ptr(), ds, T, H, W, flags,
+                                           hip.stream_ptr()), "vmg_convert_frames")
+    return dst
