@@ -238,6 +238,15 @@ int vmg_conv_wgrad3_variant(int variant);
 int vmg_linear_wgrad2_multi(int nprob, int npairs, const void* const* x, const void* const* dy, int64_t M, int64_t x_ps, int Cin, int64_t dy_ps,
                             int Cout, float* const* dW, int I_total, int o0, int i0, float* const* db, const float* scales, void* ws,
                             int64_t ws_bytes, void* stream);
+/* Which MFMA kernel the weight-gradient entry points above launched last in this process (0: none yet): kind << 24 | a << 16 | b << 8 | c.
+ * The dispatch falls back to the general kernel without an error (small workspace, few pixels, unaligned operands); a test reads this to
+ * know which kernel it has checked.  Written on the host beside each launch: nothing is added to a kernel or to the stream. */
+#define VMG_WGRAD_V1 1 /* conv_wgrad_kernel<T, KS, CT, IT>: a = KS, b = CT, c = IT */
+#define VMG_WGRAD_3 2  /* conv_wgrad3_kernel */
+#define VMG_WGRAD_3B 3 /* conv_wgrad3b_kernel */
+#define VMG_WGRAD_L2 4 /* linear_wgrad2_kernel */
+#define VMG_WGRAD_7 5  /* conv_wgrad7_kernel<CT, KS>: a = CT, b = KS */
+int vmg_conv_wgrad_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / normalisation kernels (HBM-bound, one pass, 16-byte vectors).

@@ -23,6 +23,10 @@
 namespace {
 
 constexpr int WG_MAX_PAIRS = 16;  // (x, dy) pairs summed by one launch (uses of a shared weight)
+// Which MFMA kernel this file launched last (vmg_conv_wgrad_last_kernel, include/vmg_hip.h VMG_WGRAD_*): written on the host next to every
+// launch, so that a test can tell which kernel the dispatch below picked for its shape.  kind << 24 | a << 16 | b << 8 | c.
+int g_last_kernel = 0;
+constexpr int last_kernel_id(int kind, int a = 0, int b = 0, int c = 0) { return kind << 24 | a << 16 | b << 8 | c; }
 __device__ __attribute__((aligned(256))) unsigned int g_zero_buf[64];  // 256 zero bytes: load / DMA source for out-of-image lanes
 
 // LDS-DMA (1 KiB per wave: 16 bytes per lane from a per-lane global address into a lane-linear LDS block) as an asm statement: when a
@@ -379,6 +383,7 @@ int launch_wgrad(WgradK k, hipStream_t st) {
   k.M = (long long)k.N * k.H * k.W;
   if (k.slab && (long long)gx * gy * k.S * TILE > ws_floats) k.slab = nullptr;  // (workspace too small even for one split: atomics)
   hipLaunchKernelGGL(fn, dim3(gx, gy, k.S), dim3(256), C::LDS_BYTES, st, k);
+  g_last_kernel = last_kernel_id(VMG_WGRAD_V1, KS, CT, IT);
   VMG_LAUNCH_CHECK();
   if (k.slab) {
     const long long total = (long long)gx * gy * TILE;
@@ -391,6 +396,8 @@ int launch_wgrad(WgradK k, hipStream_t st) {
 }
 
 }  // namespace
+
+extern "C" int vmg_conv_wgrad_last_kernel(void) { return g_last_kernel; }
 
 static int wgrad_impl(int dtype, int ks, int npairs, const void* const* x, const void* const* dy, int N, int H, int W, int64_t x_ps,
                       int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0, float* db, float scale, void* stream,
@@ -1387,6 +1394,7 @@ int launch_wgrad7(Wgrad7K k, float* dW, int I_total, int o0, int i0, float* db, 
     attr7[dev] = true;
   }
   hipLaunchKernelGGL(fn, dim3((unsigned)(gx * S)), dim3(W7Geo<KS>::THREADS), 2 * C::BUF, st, k);
+  g_last_kernel = last_kernel_id(VMG_WGRAD_7, CT, KS);
   VMG_LAUNCH_CHECK();
   const long long per_s = (long long)gx * C::WG_FLOATS;
   const int rb = (int)(cdiv64(per_s, 64) > 8192 ? 8192 : cdiv64(per_s, 64));
@@ -1455,9 +1463,11 @@ static int launch_wgrad3(int nprob, int npairs, const void* const* x, const void
       attr3b[dev3] = true;
     }
     hipLaunchKernelGGL(conv_wgrad3b_kernel, dim3((unsigned)(gx * gy * S * nprob)), dim3(W3_THREADS), 6 * W3_BUF, st, k);
+    g_last_kernel = last_kernel_id(VMG_WGRAD_3B);
     bias_in_pad = 1;
   } else {
     hipLaunchKernelGGL(conv_wgrad3_kernel, dim3((unsigned)(gx * gy * S * nprob)), dim3(W3_THREADS), 6 * W3_BUF, st, k);
+    g_last_kernel = last_kernel_id(VMG_WGRAD_3);
   }
   VMG_LAUNCH_CHECK();
   const long long per3 = (long long)gy * gx * W3_WG_FLOATS;
@@ -1500,6 +1510,7 @@ static int launch_lgrad2(int nprob, int npairs, const void* const* x, const void
   k.gx = gx; k.gy = gy;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(linear_wgrad2_kernel, dim3((unsigned)(gx * gy * S * nprob)), dim3(W2_THREADS), 3 * L2_BUF, st, k);
+  g_last_kernel = last_kernel_id(VMG_WGRAD_L2);
   VMG_LAUNCH_CHECK();
   const long long per_s = (long long)gy * gx * L2_WG_FLOATS;
   const int rb = (int)(cdiv64(per_s, 64) > 8192 ? 8192 : cdiv64(per_s, 64));

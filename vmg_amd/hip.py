@@ -18,6 +18,13 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_GELU = 0, 1, 2, 3
 # conv kernel routes (ConvDesc.deep, include/vmg_hip.h VMG_CONV_*)
 CONV_GENERAL, CONV_KSPLIT, CONV_WS, CONV_LINEAR_WRES, CONV_WSTAT = 0, 2, 3, 4, 6
+# weight-gradient kernels (vmg_conv_wgrad_last_kernel, include/vmg_hip.h VMG_WGRAD_*)
+WGRAD_V1, WGRAD_3, WGRAD_3B, WGRAD_L2, WGRAD_7 = 1, 2, 3, 4, 5
+
+
+def wgrad_kernel_id(kind: int, a: int = 0, b: int = 0, c: int = 0) -> int:
+    """The value vmg_conv_wgrad_last_kernel() reports: WGRAD_V1 with (KS, CT, IT), WGRAD_7 with (CT, KS), the others bare."""
+    return kind << 24 | a << 16 | b << 8 | c
 
 
 class HipError(RuntimeError):
@@ -112,6 +119,7 @@ SIGNATURES = {
     "vmg_conv_wgrad3_multi": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "vmg_conv_wgrad3_variant": (c_int, [c_int]),
+    "vmg_conv_wgrad_last_kernel": (c_int, []),
     "vmg_win3d_variant": (c_int, [c_int]),
     "vmg_linear_wgrad2_multi": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
