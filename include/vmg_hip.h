@@ -614,6 +614,14 @@ int vmg_resblock_chain_fwd_q8(const vmg_chainq8_desc* c, void* stream);
 int64_t vmg_grad_clip_ws_bytes(void);
 int vmg_grad_clip_norm(float* g, int64_t n, float max_norm, void* workspace, float* norm_out, void* stream);
 
+/* ---- bf16 payload of the data-parallel gradient exchange (the reference exchanges fp32 through DistributedDataParallel,
+ * tools/Trainer.py:30; this halves the bytes that cross the links) ---------------------------------------------------------
+ * pack: out[i] = bf16(g[i] * scale), round to nearest even, Inf and NaN pass through (scale = 1 / world is exact for 2, 4, 8 ranks).
+ * unpack: g[i] = float(in[i]).  n >= 1 elements; g, out and in are 16-byte aligned; the bf16 buffer holds n 16-bit values.
+ * One HBM-bound launch each. */
+int vmg_grad_pack_bf16(const float* g, void* out, int64_t n, float scale, void* stream);
+int vmg_grad_unpack_bf16(const void* in, float* g, int64_t n, void* stream);
+
 /* ---- Charbonnier + edge loss (reference: utils/loss.py:22-79, CharbonnierLoss(eps, if_aux_loss=True, aux_ratio)) ---------
  * x, y: (planes, H, W) fp32 images, planes = B*T*3.  fwd: a1 (planes, ceil(H/2), ceil(W/2)) scratch, ld (planes, H, W) = the
  * Laplacian of x - y (kept for the backward), partial: 2 floats per block (vmg_charbonnier_edge_blocks of them): sums of

@@ -99,7 +99,69 @@ __global__ __launch_bounds__(256) void grad_clip_scale_kernel(float* __restrict_
     for (long long i = (n4 << 2) + threadIdx.x; i < n; i += 256) g[i] *= coef;
 }
 
+// ---- bf16 payload of the data-parallel gradient exchange: out = bf16(g * scale), g = float(in) ----
+// HBM-bound streams (6 bytes per element).  A lane handles 8 elements per trip: two 16-byte loads and one 16-byte store (pack), one 16-byte
+// load and two 16-byte stores (unpack); the n % 8 elements at the end go one per lane.  Round to nearest even on the fp32 bits, as torch's
+// float -> bfloat16 does: Inf stays Inf, the largest finite fp32 rounds to Inf, NaN becomes a quiet NaN of the same sign.
+constexpr int PAYLOAD_BLOCKS = 2048;  // (256 CUs x 8 workgroups; the rest of a long buffer is walked by the grid stride)
+
+__device__ __forceinline__ unsigned bf16_bits_rne(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+__global__ __launch_bounds__(256) void grad_pack_bf16_kernel(const float* __restrict__ g, unsigned short* __restrict__ out, long long n, float scale) {
+  const long long n8 = n >> 3, stride = (long long)gridDim.x * 256;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n8; i += stride) {
+    const float4 a = reinterpret_cast<const float4*>(g)[2 * i], b = reinterpret_cast<const float4*>(g)[2 * i + 1];
+    uint4 o;
+    o.x = bf16_bits_rne(a.x * scale) | bf16_bits_rne(a.y * scale) << 16;
+    o.y = bf16_bits_rne(a.z * scale) | bf16_bits_rne(a.w * scale) << 16;
+    o.z = bf16_bits_rne(b.x * scale) | bf16_bits_rne(b.y * scale) << 16;
+    o.w = bf16_bits_rne(b.z * scale) | bf16_bits_rne(b.w * scale) << 16;
+    reinterpret_cast<uint4*>(out)[i] = o;
+  }
+  for (long long i = (n8 << 3) + blockIdx.x * 256LL + threadIdx.x; i < n; i += stride) out[i] = (unsigned short)bf16_bits_rne(g[i] * scale);
+}
+
+__global__ __launch_bounds__(256) void grad_unpack_bf16_kernel(const unsigned short* __restrict__ in, float* __restrict__ g, long long n) {
+  const long long n8 = n >> 3, stride = (long long)gridDim.x * 256;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n8; i += stride) {
+    const uint4 v = reinterpret_cast<const uint4*>(in)[i];
+    float4 a, b;
+    a.x = __uint_as_float(v.x << 16); a.y = __uint_as_float(v.x & 0xffff0000u);
+    a.z = __uint_as_float(v.y << 16); a.w = __uint_as_float(v.y & 0xffff0000u);
+    b.x = __uint_as_float(v.z << 16); b.y = __uint_as_float(v.z & 0xffff0000u);
+    b.z = __uint_as_float(v.w << 16); b.w = __uint_as_float(v.w & 0xffff0000u);
+    reinterpret_cast<float4*>(g)[2 * i] = a;
+    reinterpret_cast<float4*>(g)[2 * i + 1] = b;
+  }
+  for (long long i = (n8 << 3) + blockIdx.x * 256LL + threadIdx.x; i < n; i += stride) g[i] = __uint_as_float((unsigned)in[i] << 16);
+}
+
+static inline int payload_blocks(int64_t n) {
+  const int64_t b = cdiv64(cdiv64(n, 8), 256);
+  return (int)(b > PAYLOAD_BLOCKS ? PAYLOAD_BLOCKS : b);
+}
+
 }  // namespace
+
+extern "C" int vmg_grad_pack_bf16(const float* g, void* out, int64_t n, float scale, void* stream) {
+  VMG_CHECK(g && out && n > 0, "grad_pack_bf16: bad arguments");
+  VMG_CHECK(((uintptr_t)g % 16 == 0) && ((uintptr_t)out % 16 == 0), "grad_pack_bf16: both buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(payload_blocks(n)), dim3(256), 0, (hipStream_t)stream, g, (unsigned short*)out, (long long)n, scale);
+  VMG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vmg_grad_unpack_bf16(const void* in, float* g, int64_t n, void* stream) {
+  VMG_CHECK(in && g && n > 0, "grad_unpack_bf16: bad arguments");
+  VMG_CHECK(((uintptr_t)g % 16 == 0) && ((uintptr_t)in % 16 == 0), "grad_unpack_bf16: both buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(grad_unpack_bf16_kernel, dim3(payload_blocks(n)), dim3(256), 0, (hipStream_t)stream, (const unsigned short*)in, g, (long long)n);
+  VMG_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int64_t vmg_grad_clip_ws_bytes() { return (int64_t)CLIP_BLOCKS * sizeof(double); }
 

@@ -170,6 +170,8 @@ SIGNATURES = {
     "vmg_resblock_chain_fwd_q8": (c_int, [POINTER(ChainQ8Desc), c_void_p]),
     "vmg_grad_clip_ws_bytes": (c_int64, []),
     "vmg_grad_clip_norm": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "vmg_grad_pack_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "vmg_grad_unpack_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "vmg_tile_accumulate": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_void_p]),
     "vmg_tile_finalize": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

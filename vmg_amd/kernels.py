@@ -1474,3 +1474,22 @@ def convert_frames(src: torch.Tensor, dst: torch.Tensor, hflip: bool = False, vf
     hip.check(hip.lib().vmg_convert_frames(FRAME_TYPES[src.dtype], src.data_ptr(), ss, FRAME_TYPES[dst.dtype], dst.data_ptr(), ds, T, H, W, flags,
                                            hip.stream_ptr()), "vmg_convert_frames")
     return dst
+
+
+def grad_pack_bf16(g: torch.Tensor, out: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """vmg_grad_pack_bf16: out = bfloat16(g * scale) over two flat contiguous buffers of one length (fp32 in, bf16 out), round to nearest
+    even.  The payload of the staged data-parallel exchange (train.GradBucketReducer.exchange); one launch, nothing is synchronised."""
+    hip.require_cuda(g, out)
+    if g.dtype != torch.float32 or out.dtype != torch.bfloat16 or g.dim() != 1 or out.shape != g.shape or not (g.is_contiguous() and out.is_contiguous()):
+        raise HipError("grad_pack_bf16: a flat fp32 buffer and a flat bfloat16 buffer of the same length expected")
+    hip.check(hip.lib().vmg_grad_pack_bf16(g.data_ptr(), out.data_ptr(), g.numel(), float(scale), hip.stream_ptr()), "vmg_grad_pack_bf16")
+    return out
+
+
+def grad_unpack_bf16(payload: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """vmg_grad_unpack_bf16: g = float(payload), the inverse walk of grad_pack_bf16."""
+    hip.require_cuda(payload, g)
+    if g.dtype != torch.float32 or payload.dtype != torch.bfloat16 or g.dim() != 1 or payload.shape != g.shape or not (g.is_contiguous() and payload.is_contiguous()):
+        raise HipError("grad_unpack_bf16: a flat bfloat16 buffer and a flat fp32 buffer of the same length expected")
+    hip.check(hip.lib().vmg_grad_unpack_bf16(payload.data_ptr(), g.data_ptr(), g.numel(), hip.stream_ptr()), "vmg_grad_unpack_bf16")
+    return g

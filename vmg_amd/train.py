@@ -258,12 +258,13 @@ class GradBucketReducer:
             self.buckets.append(cur)
         if self.flat_grad is not None:
             off_of = {id(p): o for p, o in zip(self.params, offsets)}
-            self.flat = []
+            self.flat, self.bounds = [], []
             for b in self.buckets:
                 lo = min(off_of[id(p)] for p in b)
                 hi = max(off_of[id(p)] + (p.numel() + 3) // 4 * 4 for p in b)
                 if hi - lo != sum((p.numel() + 3) // 4 * 4 for p in b):
                     raise RuntimeError("GradBucketReducer: a bucket is not one contiguous slice of the flat gradient buffer")
+                self.bounds.append((lo, min(hi, self.flat_grad.numel())))
                 self.flat.append(self.flat_grad[lo:min(hi, self.flat_grad.numel())])
         else:
             self.flat = [torch.zeros(sum(p.numel() for p in b), dtype=torch.float32, device=b[0].device) for b in self.buckets]
@@ -301,7 +302,7 @@ class GradBucketReducer:
     def _on_autograd(self, p: torch.nn.Parameter):
         """autograd's post-accumulate hook.  It also fires when a backward node returned NO gradient for the parameter (the deferred
         batched weight gradients do): such parameters are complete only when wgrad.DEFERRED says so (its callback)."""
-        if id(p) not in DEFERRED.managed:
+        if self.enabled and id(p) not in DEFERRED.managed:
             self._on_grad(p)
 
     def _on_grad(self, p: torch.nn.Parameter):
@@ -334,6 +335,48 @@ class GradBucketReducer:
                     if self.side is not None:
                         torch.cuda.current_stream().wait_stream(self.side)
                     torch._foreach_copy_([p.grad.reshape(-1) for p in b], list(flat.split([p.numel() for p in b])))
+            if self.side is not None:
+                torch.cuda.current_stream().wait_stream(self.side)
+        self.reset()
+
+    def exchange(self, payload: Optional[torch.Tensor] = None):
+        """The whole exchange in one call, for a step whose backward has already run (TrainStep's two-graph replay: the gradient phase and
+        the update phase are graphs, this runs eagerly between them).  Every bucket is all-reduced in bucket INDEX order -- the same order
+        on every rank by construction, whatever order the gradients completed in -- on the side stream; the compute stream then waits for
+        the side stream (no host block with RCCL).  Averages as _launch / finish do: ReduceOp.AVG on RCCL, SUM and one divide on gloo.
+        The hooks are not involved: it works with `enabled` False and leaves pending / works / _seen reset.
+
+        payload (a flat bfloat16 buffer as long as the flat gradient buffer; RCCL only): the gradients cross the links in bfloat16 --
+        one pack of the whole buffer scaled by 1 / world (exact for 2, 4 and 8 ranks), ReduceOp.SUM over the payload's bucket slices, one
+        unpack back into the fp32 buffer.  The sum of `world` bfloat16 values is rounded to bfloat16 by the collective."""
+        if self.flat_grad is None:
+            raise RuntimeError("GradBucketReducer.exchange: needs the gradients in one flat buffer (flat_grad / a FlatAdamW optimizer)")
+        if payload is not None:
+            if not self.op_avg:
+                raise RuntimeError("GradBucketReducer.exchange: the bfloat16 payload needs the nccl (RCCL) backend")
+            if payload.dtype != torch.bfloat16 or payload.shape != self.flat_grad.shape or payload.device != self.flat_grad.device:
+                raise RuntimeError("GradBucketReducer.exchange: the payload must be a bfloat16 buffer shaped like the flat gradient buffer")
+        if self.active:
+            if self.side is not None:
+                self.side.wait_stream(torch.cuda.current_stream())
+                ctx = torch.cuda.stream(self.side)
+            else:
+                import contextlib
+                ctx = contextlib.nullcontext()
+            with ctx:
+                if payload is not None:
+                    from . import kernels as K
+                    K.grad_pack_bf16(self.flat_grad, payload, 1.0 / self.world)
+                # (not async: with RCCL a call returns once the collective is queued and the side stream waits for it; gloo blocks the host)
+                for flat, (lo, hi) in zip(self.flat, self.bounds):
+                    if payload is not None:
+                        dist.all_reduce(payload[lo:hi], op=dist.ReduceOp.SUM, group=self.group)
+                        continue
+                    dist.all_reduce(flat, op=dist.ReduceOp.AVG if self.op_avg else dist.ReduceOp.SUM, group=self.group)
+                    if not self.op_avg:
+                        flat.div_(self.world)
+                if payload is not None:
+                    K.grad_unpack_bf16(payload, self.flat_grad)
             if self.side is not None:
                 torch.cuda.current_stream().wait_stream(self.side)
         self.reset()
@@ -564,12 +607,22 @@ class TrainStep:
     def __init__(self, model: torch.nn.Module, lr: float = 2e-4, betas=(0.9, 0.99), weight_decay: float = 0.0, eps_loss: float = 1e-12,
                  aux: bool = True, aux_ratio: float = 0.005, spynet_lr: float = 0.0, distributed: bool = False,
                  bucket_bytes: int = 8 << 20, schedule: Optional[dict] = None, grad_clip: Optional[float] = None,
-                 single_rank_collectives: bool = False):
+                 single_rank_collectives: bool = False, exchange_dtype: torch.dtype = torch.float32):
         """schedule: keyword arguments of LRSchedule (T_period, restarts, weights, eta_min, warmup_iter, flow_fix, pre_lr_ratio,
         reduced_iter: the `train:` / `network.flow_fix` keys of the reference's configs) -- the learning rates are then updated after
         every optimizer step like Trainer.update_learning_rate does; None keeps them constant.
         grad_clip: max_norm of clip_grad_norm_ over ALL parameters before the optimizer step (train.if_grad_clip / grad_clip_up).
-        single_rank_collectives: see GradBucketReducer."""
+        single_rank_collectives: see GradBucketReducer.
+        exchange_dtype: torch.float32, or torch.bfloat16 = the half-size payload of the staged exchange (GradBucketReducer.exchange) of a
+        CAPTURED distributed step; RCCL ("nccl") only, gloo cannot carry bfloat16.  The eager overlapped exchange is always fp32."""
+        if exchange_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"TrainStep: exchange_dtype is torch.float32 or torch.bfloat16, got {exchange_dtype}")
+        if exchange_dtype == torch.bfloat16:
+            backend = dist.get_backend() if distributed and dist.is_initialized() else "none"
+            if backend != "nccl" or not next(model.parameters()).is_cuda:
+                raise ValueError(f"TrainStep: exchange_dtype=torch.bfloat16 needs distributed=True on the nccl (RCCL) backend with the model on the "
+                                 f"GPU; this process group's backend is '{backend}' (gloo cannot carry bfloat16)")
+        self.exchange_dtype = exchange_dtype
         self.model = model
         from . import functional as FH
         FH.set_wgrad_mode("deferred")  # batched weight gradients written straight into the flat gradient buffer
@@ -593,6 +646,9 @@ class TrainStep:
         self.iter = 0          # optimizer steps taken: the `cur_iter` of the reference's update_learning_rate
         self.grad_norm = None  # device tensor (total norm, coefficient) of the last clipped step
         self.graph = None
+        self.graph_update = None  # distributed capture: the update phase's graph (self.graph is then the gradient phase's)
+        # the bfloat16 payload of the staged exchange lives as long as the step (FlatAdamW.relayout keeps the flat length)
+        self._payload = torch.empty(self.opt.n, dtype=torch.bfloat16, device=self.opt.g.device) if exchange_dtype == torch.bfloat16 else None
         self._static = None
         self.grad_hook = None  # optional callable(TrainStep), run after the gradient exchange and before the optimizer (tests, logging)
         self.loss_args = dict(eps=eps_loss, aux=aux, aux_ratio=aux_ratio)
@@ -610,9 +666,13 @@ class TrainStep:
         Replaying the step's ~2 000 launches from a graph removes the Python / launch overhead.  The weight packs are rebuilt INSIDE the
         graph by the one-launch repack that follows the optimizer (functional.repack_all), so the packs the warm-up steps left behind are
         exactly what the first replay needs; packs that are made on demand (weights modified in place during the forward) are recorded
-        where they happen.  Single-GPU only: the bucketed all-reduce stays eager."""
+        where they happen.
+
+        With a reducer (distributed=True) the step becomes TWO graphs around the gradient exchange, and no collective is captured: graph A
+        = forward, loss, backward, deferred weight gradients; GradBucketReducer.exchange() runs eagerly on the whole flat gradient buffer
+        (fp32, or the bfloat16 payload of exchange_dtype); graph B = clip, AdamW, repack, gradient clear.  See _capture_distributed."""
         if self.reducer is not None:
-            raise RuntimeError("graph capture is for the single-GPU step; the distributed step runs eagerly")
+            return self._capture_distributed(lrs, hrs, warmup, replayer, before_capture)
         from . import functional as FH
         self._static = (lrs.clone(), hrs.clone())
         side = torch.cuda.Stream()
@@ -650,10 +710,69 @@ class TrainStep:
             self._replay, self._replay_ops, self._replay_kernels = ctypes.c_void_p(h), n_ops.value, n_k.value
         return self
 
+    def _capture_distributed(self, lrs, hrs, warmup, replayer, before_capture):
+        """capture() of the data-parallel step: graph A (gradient phase) -> eager exchange -> graph B (update phase).
+
+        The warm-up steps are ordinary eager distributed steps (overlapped exchange from the hooks), so the one-time re-layout of the flat
+        buffers by completion order has happened and the pack set has settled before anything is recorded; every rank takes the same number of
+        them (the decision to stop is agreed on, a rank that stopped early would leave the others inside a collective).  Then a barrier and a
+        device synchronisation (no collective in flight), the reducer's hooks are switched off (enabled = False: they return at once during the
+        captured backward), and the two phases are recorded.  Nothing in either capture calls torch.distributed, allocates for the reducer or
+        copies from the host.
+
+        Both captures use capture_error_mode="thread_local": a live process group has helper threads of its own (RCCL's watchdog queries events),
+        and in the default global mode a runtime query from ANY thread of the process invalidates a capture in progress.  How the runtime
+        replays the graphs is untouched."""
+        from . import functional as FH
+        if replayer:
+            raise RuntimeError("replayer=True (the csrc/replay.hip experiment) is for the single-GPU step; the distributed step replays two hipGraphs")
+        if not isinstance(self.opt, FlatAdamW):
+            raise RuntimeError("the distributed capture needs the flat optimizer (model on the GPU): the exchange runs on its gradient buffer")
+        red = self.reducer
+        self._static = (lrs.clone(), hrs.clone())
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for i in range(max(warmup, 8)):
+                stamp = FH.PACKS.stamp
+                self._eager(*self._static)
+                done = i + 1 >= warmup and FH.PACKS.settled(stamp, with_repack=True)
+                if red.active:
+                    flag = torch.tensor([int(done)], dtype=torch.int32, device=self.opt.g.device if red.op_avg else "cpu")
+                    dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=red.group)
+                    done = bool(int(flag.item()))
+                if done:
+                    break
+        torch.cuda.current_stream().wait_stream(side)
+        if red.active:
+            dist.barrier(group=red.group)
+        torch.cuda.synchronize()
+        red.enabled = False
+        red.reset()
+        if before_capture is not None:
+            before_capture()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+            self._loss = self._grad_phase(*self._static)
+        self.graph_update = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph_update, capture_error_mode="thread_local"):
+            self._update_phase(hook=False)
+        self._replay = None
+        return self
+
     def replay(self, lrs: Optional[torch.Tensor] = None, hrs: Optional[torch.Tensor] = None) -> torch.Tensor:
         if lrs is not None:
             self._static[0].copy_(lrs)
             self._static[1].copy_(hrs)
+        if self.graph_update is not None:
+            self.opt.advance()
+            self.graph.replay()                    # gradient phase: the local gradients are in the flat buffer
+            self.reducer.exchange(self._payload)   # eager, bucket index order on every rank
+            if self.grad_hook is not None:
+                self.grad_hook(self)               # host code between the graphs: sees the exchanged gradients, before the clip
+            self.graph_update.replay()             # update phase
+            self._after_update()
+            return self._loss
         if isinstance(self.opt, FlatAdamW):
             self.opt.advance()  # uploads THIS step's scalars: the learning rates the previous step's schedule.step() left in the groups
         if getattr(self, "_replay", None) is not None:
@@ -694,11 +813,28 @@ class TrainStep:
             if grad_acc != 1 or not update:
                 raise RuntimeError("the captured step is one whole update; gradient accumulation runs eagerly")
             return self.replay(lrs, hrs)
+        if self.exchange_dtype != torch.float32:
+            raise RuntimeError("exchange_dtype=torch.bfloat16 belongs to the staged exchange of a captured step: call capture() first "
+                               "(the eager overlapped exchange is fp32)")
         return self._eager(lrs, hrs, grad_acc, update)
 
     def _eager(self, lrs: torch.Tensor, hrs: torch.Tensor, grad_acc: int = 1, update: bool = True) -> torch.Tensor:
         if self.reducer is not None:
             self.reducer.enabled = bool(update)
+        loss = self._grad_phase(lrs, hrs, grad_acc)
+        if update and self.reducer is not None:
+            self.reducer.finish()
+        done = self._update_phase(update)
+        if not done:
+            return loss.detach()
+        if not (loss.is_cuda and torch.cuda.is_current_stream_capturing()):
+            self._after_update()  # (the capture pass runs no kernels: it is not a step; replay() does the bookkeeping per replayed step)
+        if self.reducer is not None:
+            self.reducer.relayout_by_completion()  # once, after the first step: buckets follow the measured completion order
+        return loss.detach()
+
+    def _grad_phase(self, lrs: torch.Tensor, hrs: torch.Tensor, grad_acc: int = 1) -> torch.Tensor:
+        """Model, loss, backward, deferred weight-gradient flush: the local gradients are in place afterwards."""
         out = self.model(lrs)
         if out.is_cuda and self.loss_args["aux"]:
             loss = charbonnier_edge_loss_hip(out.float(), hrs.float(), self.loss_args["eps"], self.loss_args["aux_ratio"])
@@ -708,8 +844,11 @@ class TrainStep:
             loss = loss / grad_acc
         loss.backward()
         self._flush()
-        if update and self.reducer is not None:
-            self.reducer.finish()
+        return loss
+
+    def _update_phase(self, update: bool = True, hook: bool = True) -> bool:
+        """Clip, grad_hook, optimizer, weight repack, gradient clear.  Returns False for a non-updating micro-step (it only clips).
+        hook=False: the update graph of the distributed capture -- replay() runs the hook on the host between the two graphs."""
         if self.grad_clip is not None:
             # the reference clips after EVERY micro-step's backward (tools/Trainer.py:166-167, 179-180), i.e. the partially accumulated sum is
             # rescaled each time -- reproduced as is.  (Data-parallel: its non-updating micro-steps clip the all-reduced partial sum, ours the
@@ -719,8 +858,8 @@ class TrainStep:
             else:
                 self.grad_norm = torch.nn.utils.clip_grad_norm_([p for g in self.opt.param_groups for p in g["params"]], self.grad_clip, norm_type=2)
         if not update:
-            return loss.detach()
-        if self.grad_hook is not None:
+            return False
+        if hook and self.grad_hook is not None:
             self.grad_hook(self)
         if isinstance(self.opt, FlatAdamW):
             if self.graph is None and not torch.cuda.is_current_stream_capturing():
@@ -732,8 +871,4 @@ class TrainStep:
         else:
             self.opt.step()
         self.opt.zero_grad(set_to_none=True)
-        if not (loss.is_cuda and torch.cuda.is_current_stream_capturing()):
-            self._after_update()  # (the capture pass runs no kernels: it is not a step; replay() does the bookkeeping per replayed step)
-        if self.reducer is not None:
-            self.reducer.relayout_by_completion()  # once, after the first step: buckets follow the measured completion order
-        return loss.detach()
+        return True
