@@ -213,9 +213,18 @@ int vmg_conv_wgrad_batched(int dtype, int ks, int npairs, const void* const* x, 
                            int64_t x_ps, int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0, float* db,
                            float scale, void* stream);
 
-/* The same with a caller-provided workspace (vmg_conv_wgrad_ws_bytes() bytes, reusable across calls on one stream): bf16 3x3
- * gradients then take the large-tile kernel (144 x 48 x 9 outputs per workgroup, partial slabs + ordered reduction: bitwise
- * reproducible, no atomics); every other case falls through to vmg_conv_wgrad_batched. */
+/* The same with a caller-provided workspace (vmg_conv_wgrad_ws_bytes() bytes, reusable across calls on one stream).  The first rule that
+ * holds picks the kernel; a kernel that stores its K splits as slabs in the workspace needs room for them there, and a rule whose slabs do
+ * not fit does not hold.  "Aligned": every pointer of the call on a 16-byte boundary.
+ *   1. bf16 1x1; Cin, Cout and both pixel strides multiples of 8; x and dy aligned; at least 64 units of 32 pixels over all pairs
+ *        -> linear_wgrad2_kernel (144 x 144 outputs per workgroup; slabs + ordered reduction: bitwise reproducible, no atomics)
+ *   2. bf16 7x7 with Cout <= 64 or 3x3 with Cout <= 16; Cin and x's pixel stride multiples of 8; x aligned, dy on a 2-byte boundary
+ *      (any dy stride: read as vectors when it is a multiple of 8 and dy is aligned, else element by element); fewer than 2^30 K units
+ *        -> conv_wgrad7_kernel (one wave per tap row; slabs)
+ *   3. bf16 3x3 with Cout > 16; both pixel strides multiples of 8 and no smaller than the channel counts rounded up to 8; x and dy aligned
+ *        -> conv_wgrad3b_kernel, or conv_wgrad3_kernel under vmg_conv_wgrad3_variant(0) or when a pair's tensors reach 2^31 bytes
+ *           (144 x 48 x 9 outputs per workgroup; slabs)
+ *   4. anything else -> the kernel of vmg_conv_wgrad_batched, with float atomics; 7x7 with a workspace of at least 1 MiB: slabs. */
 int64_t vmg_conv_wgrad_ws_bytes(void);
 int vmg_conv_wgrad_batched_ws(int dtype, int ks, int npairs, const void* const* x, const void* const* dy, int N, int H, int W,
                               int64_t x_ps, int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0, float* db,
@@ -247,6 +256,21 @@ int vmg_linear_wgrad2_multi(int nprob, int npairs, const void* const* x, const v
 #define VMG_WGRAD_L2 4 /* linear_wgrad2_kernel */
 #define VMG_WGRAD_7 5  /* conv_wgrad7_kernel<CT, KS>: a = CT, b = KS */
 int vmg_conv_wgrad_last_kernel(void);
+/* The decision behind every entry point above, without a launch (pure: no device needed): which kernel the entry `entry` would run for a
+ * call of this shape, and with which grid.  align: VMG_WGRAD_ALIGN_* facts about the call's x / dy pointers; ws_bytes: 0 without a
+ * workspace; a linear call of M pixels is N = H = 1, W = M.  Writes VMG_WGRAD_PLAN_INTS ints to plan: the kernel as
+ * vmg_conv_wgrad_last_kernel reports it (0: a multi entry whose large-tile kernel does not apply -- the entry fails), co blocks, ci
+ * blocks, K splits, workgroups of the main launch, 1 for slabs + reduce kernel or 0 for float atomics, blocks of the reduce launch.
+ * Returns -1 for the arguments the entry rejects. */
+#define VMG_WGRAD_ENTRY_PLAIN 0 /* vmg_conv_wgrad, vmg_conv_wgrad_batched */
+#define VMG_WGRAD_ENTRY_WS 1    /* vmg_conv_wgrad_batched_ws */
+#define VMG_WGRAD_ENTRY_MULTI 2 /* vmg_conv_wgrad3_multi (ks 3), vmg_linear_wgrad2_multi (ks 1) */
+#define VMG_WGRAD_ALIGN_X16 1   /* every x pointer is 16-byte aligned */
+#define VMG_WGRAD_ALIGN_DY16 2  /* every dy pointer is 16-byte aligned */
+#define VMG_WGRAD_ALIGN_DY2 4   /* every dy pointer is 2-byte aligned */
+#define VMG_WGRAD_PLAN_INTS 7
+int vmg_conv_wgrad_plan(int entry, int dtype, int ks, int nprob, int npairs, int N, int H, int W, int64_t x_ps, int Cin, int64_t dy_ps, int Cout,
+                        int I_total, int o0, int i0, int align, int64_t ws_bytes, int* plan);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / normalisation kernels (HBM-bound, one pass, 16-byte vectors).

@@ -360,7 +360,7 @@ def test_tap_row_kernel_into_a_slice_of_a_wider_parameter():
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
-# the general ("v1") kernel conv_wgrad_kernel: every instantiation of wgrad_impl
+# the general ("v1") kernel conv_wgrad_kernel: every instantiation wgrad_plan picks
 # ------------------------------------------------------------------------------------------------------------------------------------
 V1_SHAPES = [(1, 3, 33, 8, 16), (1, 3, 33, 40, 56), (1, 3, 33, 144, 48), (2, 1, 70, 24, 24)]
 

@@ -16,6 +16,7 @@
 // flight while the current one is multiplied).  At the end the 4 waves' accumulators are summed with LDS float
 // atomics into a [co][ci][tap] image = the OIHW order, and written out with coalesced global float atomics.
 #include <stdlib.h>
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -357,108 +358,7 @@ __global__ void wgrad_slab_reduce_kernel(const float* __restrict__ slab, int S, 
   }
 }
 
-template <typename T, int KS, int CT, int IT, int UR = 1>
-int launch_wgrad(WgradK k, hipStream_t st) {
-  using C = WgradCfg<T, KS, CT, IT, UR>;
-  static_assert(C::LDS_BYTES <= 160 * 1024, "wgrad LDS");
-  const int gx = cdiv(k.Cout, C::DYC), gy = cdiv(k.Cin, C::XC);
-  long long s = 1024 / ((long long)gx * gy);  // ~4 workgroups per CU in flight
-  if (s > k.U / 32) s = k.U / 32;           // >= 8 K units per wave, or the float-atomic epilogue dominates
-  constexpr long long TILE = C::DYC * C::XC * C::KK + C::DYC;
-  if (k.slab) {  // the K splits must fit the workspace
-    const long long cap = k.M /* = workspace floats here, see wgrad_impl */ / ((long long)gx * gy * TILE);
-    if (s > cap) s = cap;
-  }
-  if (s < 1) s = 1;
-  if (s > 65535) s = 65535;
-  k.S = (int)s;
-  auto fn = conv_wgrad_kernel<T, KS, CT, IT, UR>;
-  static bool attr_set[VMG_MAX_DEVICES] = {};  // the attribute is per device
-  const int dev = vmg_current_device();
-  if (!attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set[dev] = true;
-  }
-  const long long ws_floats = k.slab ? k.M : 0;
-  k.M = (long long)k.N * k.H * k.W;
-  if (k.slab && (long long)gx * gy * k.S * TILE > ws_floats) k.slab = nullptr;  // (workspace too small even for one split: atomics)
-  hipLaunchKernelGGL(fn, dim3(gx, gy, k.S), dim3(256), C::LDS_BYTES, st, k);
-  g_last_kernel = last_kernel_id(VMG_WGRAD_V1, KS, CT, IT);
-  VMG_LAUNCH_CHECK();
-  if (k.slab) {
-    const long long total = (long long)gx * gy * TILE;
-    const int rb = (int)(cdiv64(total, 256) > 4096 ? 4096 : cdiv64(total, 256));
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3(rb), dim3(256), 0, st, (const float*)k.slab, k.S, gx, gy, C::DYC, C::XC, C::KK, k.Cout, k.Cin, k.dW,
-                       k.I_total, k.o0, k.i0, k.db, k.scale);
-    VMG_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
 }  // namespace
-
-extern "C" int vmg_conv_wgrad_last_kernel(void) { return g_last_kernel; }
-
-static int wgrad_impl(int dtype, int ks, int npairs, const void* const* x, const void* const* dy, int N, int H, int W, int64_t x_ps,
-                      int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0, float* db, float scale, void* stream,
-                      float* ws = nullptr, int64_t ws_bytes = 0) {
-  VMG_CHECK(ks == 1 || ks == 3 || ks == 7, "conv_wgrad: ks must be 1, 3 or 7");
-  VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "conv_wgrad: bad dtype");
-  VMG_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv_wgrad: bad shape");
-  VMG_CHECK(npairs >= 1 && npairs <= WG_MAX_PAIRS && x && dy && dW, "conv_wgrad: 1..%d (x, dy) pairs", WG_MAX_PAIRS);
-  VMG_CHECK(x_ps >= Cin && dy_ps >= Cout && i0 >= 0 && i0 + Cin <= I_total && o0 >= 0, "conv_wgrad: bad strides / slices");
-  const int es = dtype == VMG_BF16 ? 2 : 4, vpl = 16 / es;
-  WgradK k;
-  memset(&k, 0, sizeof(k));
-  // 16-byte vector loads need a pixel stride that is a multiple of the vector (then a vector that starts inside the channel range ends
-  // inside the pixel's stride: a zero-padded or wider tensor behind a channel slice, e.g. the 3-channel output gradient of conv_last
-  // padded to 8) and aligned bases; channel counts need not be multiples of 8
-  k.vec_x = (x_ps % vpl == 0);
-  k.vec_dy = (dy_ps % vpl == 0);
-  for (int p = 0; p < npairs; ++p) {
-    VMG_CHECK(x[p] && dy[p], "conv_wgrad: null pointer in pair %d", p);
-    k.x[p] = (const char*)x[p];
-    k.dy[p] = (const char*)dy[p];
-    k.vec_x = k.vec_x && ((uintptr_t)x[p] % 16 == 0);
-    k.vec_dy = k.vec_dy && ((uintptr_t)dy[p] % 16 == 0);
-  }
-  k.npairs = npairs;
-  k.x_ps = x_ps; k.Cin = Cin; k.dy_ps = dy_ps; k.Cout = Cout;
-  k.dW = dW; k.I_total = I_total; k.o0 = o0; k.i0 = i0; k.db = db; k.scale = scale;
-  k.N = N; k.H = H; k.W = W; k.M = (long long)N * H * W;
-  k.SEG = cdiv(W, 32);
-  const int ur = 1;  // rows per K unit (must match the launch below; 2 and 4 rows spilled registers in the 49-tap instantiations)
-  k.HB = cdiv(H, ur);
-  k.Upair = ks > 1 ? (long long)N * k.HB * k.SEG : cdiv64(k.M, 32);
-  k.U = k.Upair * npairs;
-  hipStream_t st = (hipStream_t)stream;
-  if (ks == 7) {  // 49 taps x one 16 x 16 tile per workgroup; K splits reduced through the workspace when there is one
-    if (ws && ws_bytes >= (1 << 20)) {
-      k.slab = ws;
-      k.M = ws_bytes / 4;  // (launch_wgrad reads the workspace size from here and restores M)
-    }
-    return dtype == VMG_BF16 ? launch_wgrad<bf16, 7, 1, 1, 1>(k, st) : launch_wgrad<float, 7, 1, 1, 1>(k, st);
-  }
-  if (dtype == VMG_BF16 && ks == 3 && Cout <= 16) {  // (conv_last: 64 -> 3 on 1.8 M pixels; 64 input channels per workgroup: whole 128-byte pixel rows of X)
-    // (only without a workspace: vmg_conv_wgrad_batched_ws sends this shape to the three-wave instance of conv_wgrad7_kernel, 122 us
-    //  instead of 470-560 here, where ~650 address instructions per K unit and one wave per SIMD leave the loads exposed)
-    return Cin >= 64 ? launch_wgrad<bf16, 3, 1, 4>(k, st) : launch_wgrad<bf16, 3, 1, 1>(k, st);
-  }
-  if (dtype == VMG_BF16) return ks == 3 ? launch_wgrad<bf16, 3, 3, 1>(k, st) : launch_wgrad<bf16, 1, 3, 3>(k, st);
-  return ks == 3 ? launch_wgrad<float, 3, 3, 1>(k, st) : launch_wgrad<float, 1, 3, 3>(k, st);
-}
-
-extern "C" int vmg_conv_wgrad(int dtype, int ks, int N, int H, int W, const void* x, int64_t x_ps, int Cin, const void* dy,
-                              int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0, float* db, float scale,
-                              void* stream) {
-  return wgrad_impl(dtype, ks, 1, &x, &dy, N, H, W, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scale, stream);
-}
-
-extern "C" int vmg_conv_wgrad_batched(int dtype, int ks, int npairs, const void* const* x, const void* const* dy, int N, int H, int W,
-                                      int64_t x_ps, int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0,
-                                      float* db, float scale, void* stream) {
-  return wgrad_impl(dtype, ks, npairs, x, dy, N, H, W, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scale, stream);
-}
 
 // =====================================================================================================
 // Large-tile kernels (bf16): shared LDS tiles, slab reduction.
@@ -1375,220 +1275,335 @@ __global__ __launch_bounds__(256) void conv_wgrad7_reduce_kernel(const float* __
   }
 }
 
-template <int CT, int KS = 7>
-int launch_wgrad7(Wgrad7K k, float* dW, int I_total, int o0, int i0, float* db, float scale, int64_t ws_bytes, hipStream_t st) {
-  using C = W7Cfg<CT, KS>;
-  const int gx = cdiv(k.Cin, 16);
-  long long S = 512 / gx;            // ~two rounds of workgroups over the 256 CUs
-  if (S > k.U / 2) S = k.U / 2;      // >= 2 units per workgroup
-  const long long cap = ws_bytes / ((long long)gx * C::WG_FLOATS * 4);
-  if (S > cap) S = cap;
-  if (S < 1) S = 1;
-  if (cap < 1) return 1;  // (workspace too small: the caller falls back)
-  k.S = (int)S; k.gx = gx;
-  auto fn = conv_wgrad7_kernel<CT, KS>;
-  static bool attr7[VMG_MAX_DEVICES] = {};  // per instantiation and device
-  const int dev = vmg_current_device();
-  if (!attr7[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * C::BUF);
-    attr7[dev] = true;
+// =====================================================================================================
+// Host side.  Every entry point fills one WgradCall, then: wgrad_validate (the hard errors) -> wgrad_plan (which kernel, which grid;
+// a pure function of integers, also exported as vmg_conv_wgrad_plan) -> wgrad_launch (fills the kernel's argument struct and launches).
+// =====================================================================================================
+constexpr int WG_NULL = 8;  // beside the VMG_WGRAD_ALIGN_* facts: a pointer the entry needs is null
+
+struct WgradCall {
+  int entry, dtype, ks, nprob, npairs;
+  const void* const* x;   // [problem][pair]
+  const void* const* dy;
+  int N, H, W;            // (0 from vmg_linear_wgrad2_multi, which knows only M)
+  long long M;            // pixels per pair
+  long long x_ps, dy_ps;
+  int Cin, Cout;
+  float* const* dW;       // per problem
+  float* const* db;       // per problem; the table or an entry may be null
+  const float* scale;     // per problem
+  int I_total, o0, i0;
+  void* ws;
+  long long ws_bytes;     // 0 without a workspace
+};
+
+struct WgradPlan {
+  int kernel;       // as vmg_conv_wgrad_last_kernel reports it; 0: the large-tile kernel of a multi entry does not apply
+  int gx, gy, S;    // co blocks, ci blocks, K splits
+  long long wgs;    // workgroups of the main launch
+  int slabs;        // 1: partial sums to the workspace and a reduce kernel, 0: float atomics
+  int rblocks;      // blocks of the reduce launch (x nprob)
+};
+
+long long pixels(int N, int H, int W) { return N > 0 && H > 0 && W > 0 ? (long long)N * H * W : 0; }
+
+// Alignment facts of a call's pointers, WG_NULL if one is missing.  (Counts out of range: nothing is read, wgrad_validate rejects the call.)
+int wgrad_pointer_facts(const WgradCall& d) {
+  if (!d.x || !d.dy || !d.dW || !d.scale || (d.entry == VMG_WGRAD_ENTRY_MULTI && !d.ws)) return WG_NULL;
+  if (d.nprob < 1 || d.nprob > W3_MAX_PROBS || d.npairs < 1 || d.npairs > WG_MAX_PAIRS) return 0;
+  int f = VMG_WGRAD_ALIGN_X16 | VMG_WGRAD_ALIGN_DY16 | VMG_WGRAD_ALIGN_DY2;
+  for (int p = 0; p < d.nprob * d.npairs; ++p) {
+    if (!d.x[p] || !d.dy[p]) return WG_NULL;
+    if ((uintptr_t)d.x[p] % 16) f &= ~VMG_WGRAD_ALIGN_X16;
+    if ((uintptr_t)d.dy[p] % 16) f &= ~VMG_WGRAD_ALIGN_DY16;
+    if ((uintptr_t)d.dy[p] % 2) f &= ~VMG_WGRAD_ALIGN_DY2;
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)(gx * S)), dim3(W7Geo<KS>::THREADS), 2 * C::BUF, st, k);
-  g_last_kernel = last_kernel_id(VMG_WGRAD_7, CT, KS);
+  for (int q = 0; q < d.nprob; ++q)
+    if (!d.dW[q]) return WG_NULL;
+  return f;
+}
+
+// The hard errors.  What only keeps a problem from a fast kernel is none: wgrad_plan then picks the general kernel, or no kernel for
+// the multi entries, which have no general kernel to fall back to and fail.
+int wgrad_validate(const WgradCall& d, int facts) {
+  const bool multi = d.entry == VMG_WGRAD_ENTRY_MULTI;
+  VMG_CHECK(d.ks == 1 || d.ks == 3 || d.ks == 7, "conv_wgrad: ks must be 1, 3 or 7");
+  VMG_CHECK(d.dtype == VMG_F32 || d.dtype == VMG_BF16, "conv_wgrad: bad dtype");
+  VMG_CHECK(d.M > 0 && d.Cin > 0 && d.Cout > 0, "conv_wgrad: bad shape");
+  VMG_CHECK(d.nprob >= 1 && d.nprob <= (multi ? W3_MAX_PROBS : 1) && d.npairs >= 1 && d.npairs <= WG_MAX_PAIRS, "conv_wgrad: 1..%d problems, 1..%d (x, dy) pairs",
+            W3_MAX_PROBS, WG_MAX_PAIRS);
+  VMG_CHECK(!(facts & WG_NULL), "conv_wgrad: null pointer");
+  VMG_CHECK(d.x_ps >= d.Cin && d.dy_ps >= d.Cout && d.i0 >= 0 && d.i0 + d.Cin <= d.I_total && d.o0 >= 0, "conv_wgrad: bad strides / slices");
+  return 0;
+}
+
+constexpr int w7_ct(int ks, int Cout) { return ks == 3 || Cout <= 16 ? 1 : Cout <= 32 ? 2 : 4; }
+constexpr long long w7_wg_floats(int ks, int ct) { return (long long)(ks * ks * ct + ct) * 256; }
+constexpr long long reduce_blocks(long long elems, int per_block, int most) { return (elems + per_block - 1) / per_block > most ? most : (elems + per_block - 1) / per_block; }
+
+// Which kernel serves the call, and with which grid.  Pure: integers in, integers out (variant = g_w3_variant).  Rules in order; all
+// divisions are integer divisions.
+WgradPlan wgrad_plan(const WgradCall& d, int variant, int facts) {
+  const bool multi = d.entry == VMG_WGRAD_ENTRY_MULTI, bf = d.dtype == VMG_BF16;
+  const bool x16 = facts & VMG_WGRAD_ALIGN_X16, dy16 = facts & VMG_WGRAD_ALIGN_DY16, dy2 = facts & VMG_WGRAD_ALIGN_DY2;
+  const bool xs8 = d.x_ps % 8 == 0, dys8 = d.dy_ps % 8 == 0;
+  const long long ws_bytes = d.entry == VMG_WGRAD_ENTRY_PLAIN ? 0 : d.ws_bytes;  // (0: no rule below finds room for a slab)
+  const int seg = cdiv(d.W, 32);
+  WgradPlan p = {};
+  auto slabs = [&p](int kernel, long long S, long long groups, long long slab) {  // groups: workgroups, slab: floats, both per K split (and problem)
+    p.kernel = kernel; p.S = (int)S; p.wgs = groups * S; p.slabs = 1; p.rblocks = (int)reduce_blocks(slab, 64, 8192);
+    return p;
+  };
+  // 1. 1x1 large tile (linear_wgrad2_kernel): every channel count and stride in whole 16-byte vectors, at least 64 units of 32 pixels
+  //    (fewer: the general kernel's single launch is cheaper)
+  if (bf && d.ks == 1 && xs8 && dys8 && d.Cin % 8 == 0 && d.Cout % 8 == 0 && x16 && dy16) {
+    const long long U = cdiv64(d.M, 32) * d.npairs;
+    p.gx = cdiv(d.Cout, 144); p.gy = cdiv(d.Cin, 144);
+    const long long groups = (long long)p.gx * p.gy * d.nprob, slab = p.gx * p.gy * L2_WG_FLOATS;
+    const long long S = std::max(1LL, std::min(512 / groups, U / 8));  // two workgroups per CU over all problems
+    if (U >= 64 && d.nprob * S * slab * 4 <= ws_bytes) return slabs(last_kernel_id(VMG_WGRAD_L2), S, groups, slab);
+  }
+  // 2. one wave per tap row (conv_wgrad7_kernel): 7x7 with <= 64 output channels, 3x3 with <= 16 (the 144-channel tile would be 9/10
+  //    padding).  dY may be unaligned and of any stride (then read element by element: the 2-channel flow head); channels of X past
+  //    Cin would be multiplied, so Cin itself is a multiple of 8
+  if (!multi && bf && ((d.ks == 7 && d.Cout <= 64) || (d.ks == 3 && d.Cout <= 16)) && xs8 && d.Cin % 8 == 0 && x16 && dy2) {
+    const long long U = (long long)d.npairs * d.N * cdiv(d.H, d.ks == 7 ? W7Geo<7>::R : W7Geo<3>::R) * seg;
+    const int ct = w7_ct(d.ks, d.Cout);
+    p.gx = cdiv(d.Cin, 16); p.gy = 1;
+    const long long slab = p.gx * w7_wg_floats(d.ks, ct), cap = ws_bytes / (slab * 4);
+    // ~two rounds of workgroups over the 256 CUs, >= 2 units each
+    if (U < (1LL << 30) && cap >= 1) return slabs(last_kernel_id(VMG_WGRAD_7, ct, d.ks), std::max(1LL, std::min({512LL / p.gx, U / 2, cap})), p.gx, slab);
+  }
+  // 3. 3x3 large tile: 8-channel vectors that may run past the channel count when the pixel stride has room for the whole last vector
+  //    (the zero-padded input of the 3-channel stem conv, a slice of a wider tensor: the extra channels are computed and dropped)
+  if (bf && d.ks == 3 && (multi || d.Cout > 16) && xs8 && dys8 && d.x_ps >= ((d.Cin + 7) & ~7) && d.dy_ps >= ((d.Cout + 7) & ~7) && x16 && dy16) {
+    const long long U = (long long)d.N * d.H * seg * d.npairs;
+    p.gx = cdiv(d.Cout, W2_DYC); p.gy = cdiv(d.Cin, W2_XC);
+    const long long groups = (long long)p.gx * p.gy * d.nprob, slab = p.gx * p.gy * W3_WG_FLOATS;
+    const long long S = std::max(1LL, std::min(256 / groups, U / 8));  // one workgroup per CU over all problems
+    // the buffer-addressed variant needs every byte of a pair's tensors (plus the X tile's reach of two rows and 34 pixels) below 2^31 from the base
+    const long long reach = (d.M + 2LL * d.W + 40) * std::max(d.x_ps, d.dy_ps) * 2;
+    if (d.nprob * S * slab * 4 <= ws_bytes) return slabs(last_kernel_id(variant == 1 && reach < (1LL << 31) ? VMG_WGRAD_3B : VMG_WGRAD_3), S, groups, slab);
+  }
+  if (multi) return WgradPlan{};  // (no large-tile kernel: the entry fails)
+  // 4. the general kernel.  bf16 3x3 with <= 16 output channels: one co tile, and 64 input channels per workgroup (whole 128-byte pixel
+  //    rows of X) when there are that many.  Float atomics, except 7x7 with a workspace of >= 1 MiB: 49 taps x one 16 x 16 tile per
+  //    workgroup, few (co, ci) tiles and many K splits, whose atomics would all hit the same few addresses
+  const int small3 = bf && d.ks == 3 && d.Cout <= 16;
+  const int ct = d.ks == 7 || small3 ? 1 : 3, it = d.ks == 1 ? 3 : small3 && d.Cin >= 64 ? 4 : 1;
+  const long long U = (d.ks > 1 ? (long long)d.N * d.H * seg : cdiv64(d.M, 32)) * d.npairs;
+  p.gx = cdiv(d.Cout, ct * 16); p.gy = cdiv(d.Cin, it * 16);
+  const long long slab = (long long)p.gx * p.gy * (ct * 16 * it * 16 * d.ks * d.ks + ct * 16), ws_floats = ws_bytes / 4;  // slab: floats of one K split
+  long long S = std::min(1024 / ((long long)p.gx * p.gy), U / 32);  // ~4 workgroups per CU in flight; >= 8 K units per wave, or the epilogue dominates
+  p.slabs = d.ks == 7 && ws_bytes >= (1 << 20);
+  if (p.slabs) S = std::min(S, ws_floats / slab);
+  S = std::max(1LL, std::min(S, 65535LL));
+  if (p.slabs && S * slab > ws_floats) p.slabs = 0;  // (not even one split fits)
+  p.kernel = last_kernel_id(VMG_WGRAD_V1, d.ks, ct, it); p.S = (int)S; p.wgs = p.gx * p.gy * S;
+  p.rblocks = p.slabs ? (int)reduce_blocks(slab, 256, 4096) : 0;
+  return p;
+}
+
+// The dynamic-LDS limit of a kernel, set once per kernel and device.
+template <auto Kernel>
+void allow_lds(int bytes) {
+  static bool done[VMG_MAX_DEVICES] = {};
+  const int dev = vmg_current_device();
+  if (done[dev]) return;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  done[dev] = true;
+}
+
+template <typename T, int KS, int CT, int IT>
+int launch_v1(const WgradCall& d, const WgradPlan& p, int facts, hipStream_t st) {
+  using C = WgradCfg<T, KS, CT, IT>;
+  static_assert(C::LDS_BYTES <= 160 * 1024, "wgrad LDS");
+  WgradK k;
+  memset(&k, 0, sizeof(k));
+  // 16-byte vector loads need a pixel stride that is a multiple of the vector (then a vector that starts inside the channel range ends
+  // inside the pixel's stride: a zero-padded or wider tensor behind a channel slice, e.g. the 3-channel output gradient of conv_last
+  // padded to 8) and aligned bases; channel counts need not be multiples of 8
+  k.vec_x = d.x_ps % C::VPL == 0 && (facts & VMG_WGRAD_ALIGN_X16);
+  k.vec_dy = d.dy_ps % C::VPL == 0 && (facts & VMG_WGRAD_ALIGN_DY16);
+  for (int i = 0; i < d.npairs; ++i) { k.x[i] = (const char*)d.x[i]; k.dy[i] = (const char*)d.dy[i]; }
+  k.npairs = d.npairs;
+  k.x_ps = d.x_ps; k.Cin = d.Cin; k.dy_ps = d.dy_ps; k.Cout = d.Cout;
+  k.dW = d.dW[0]; k.I_total = d.I_total; k.o0 = d.o0; k.i0 = d.i0; k.db = d.db ? d.db[0] : nullptr; k.scale = d.scale[0];
+  k.N = d.N; k.H = d.H; k.W = d.W; k.M = d.M;
+  k.SEG = cdiv(d.W, 32);
+  k.HB = d.H;  // one row per K unit (2 and 4 rows spilled registers in the 49-tap instantiations)
+  k.Upair = KS > 1 ? (long long)d.N * k.HB * k.SEG : cdiv64(k.M, 32);
+  k.U = k.Upair * d.npairs;
+  k.S = p.S;
+  k.slab = p.slabs ? (float*)d.ws : nullptr;
+  allow_lds<conv_wgrad_kernel<T, KS, CT, IT>>(160 * 1024);
+  hipLaunchKernelGGL((conv_wgrad_kernel<T, KS, CT, IT>), dim3(p.gx, p.gy, p.S), dim3(256), C::LDS_BYTES, st, k);
   VMG_LAUNCH_CHECK();
-  const long long per_s = (long long)gx * C::WG_FLOATS;
-  const int rb = (int)(cdiv64(per_s, 64) > 8192 ? 8192 : cdiv64(per_s, 64));
-  hipLaunchKernelGGL(conv_wgrad7_reduce_kernel, dim3(rb), dim3(256), 0, st, (const float*)k.slab, (int)S, gx, CT, KS, k.Cin, k.Cout, dW, I_total, o0, i0, db, scale);
+  if (p.slabs) {
+    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3(p.rblocks), dim3(256), 0, st, (const float*)k.slab, k.S, p.gx, p.gy, C::DYC, C::XC, C::KK, k.Cout, k.Cin, k.dW,
+                       k.I_total, k.o0, k.i0, k.db, k.scale);
+    VMG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+template <int CT, int KS>
+int launch_w7(const WgradCall& d, const WgradPlan& p, int facts, hipStream_t st) {
+  using C = W7Cfg<CT, KS>;
+  static_assert(C::WG_FLOATS == w7_wg_floats(KS, CT), "wgrad_plan sizes the tap-row kernel's slabs");
+  Wgrad7K k;
+  memset(&k, 0, sizeof(k));
+  for (int i = 0; i < d.npairs; ++i) { k.x[i] = (const char*)d.x[i]; k.dy[i] = (const char*)d.dy[i]; }
+  k.npairs = d.npairs; k.x_ps = d.x_ps; k.dy_ps = d.dy_ps; k.Cin = d.Cin; k.Cout = d.Cout; k.slab = (float*)d.ws;
+  k.vec_dy = d.dy_ps % 8 == 0 && (facts & VMG_WGRAD_ALIGN_DY16);  // (channels past Cout inside the last vector are computed and dropped)
+  k.N = d.N; k.H = d.H; k.W = d.W; k.SEG = cdiv(d.W, 32); k.HB = cdiv(d.H, W7Geo<KS>::R);
+  k.Upair = d.N * k.HB * k.SEG; k.U = k.Upair * d.npairs;
+  k.has_bias = d.db && d.db[0];
+  k.S = p.S; k.gx = p.gx;
+  allow_lds<conv_wgrad7_kernel<CT, KS>>(2 * C::BUF);
+  hipLaunchKernelGGL((conv_wgrad7_kernel<CT, KS>), dim3((unsigned)p.wgs), dim3(W7Geo<KS>::THREADS), 2 * C::BUF, st, k);
+  VMG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(conv_wgrad7_reduce_kernel, dim3(p.rblocks), dim3(256), 0, st, (const float*)k.slab, p.S, p.gx, CT, KS, k.Cin, k.Cout, d.dW[0], d.I_total, d.o0,
+                     d.i0, d.db ? d.db[0] : nullptr, d.scale[0]);
   VMG_LAUNCH_CHECK();
   return 0;
 }
 
+// What Wgrad2K and Lgrad2K share: the [problem][pair] pointer table, the counts and strides, the plan's grid; and the reduce kernel's outputs.
+template <typename K>
+void fill_problems(K& k, Wgrad3Out& outs, const WgradCall& d, const WgradPlan& p) {
+  memset(&k, 0, sizeof(k));
+  memset(&outs, 0, sizeof(outs));
+  for (int q = 0; q < d.nprob; ++q) {
+    for (int i = 0; i < d.npairs; ++i) {
+      k.x[q * WG_MAX_PAIRS + i] = (const char*)d.x[q * d.npairs + i];
+      k.dy[q * WG_MAX_PAIRS + i] = (const char*)d.dy[q * d.npairs + i];
+    }
+    outs.dW[q] = d.dW[q];
+    outs.db[q] = d.db ? d.db[q] : nullptr;
+    outs.scale[q] = d.scale[q];
+    k.has_bias = k.has_bias || outs.db[q] != nullptr;
+  }
+  k.npairs = d.npairs; k.nprob = d.nprob; k.x_ps = d.x_ps; k.dy_ps = d.dy_ps;
+  k.S = p.S; k.slab = (float*)d.ws; k.gx = p.gx; k.gy = p.gy;
+}
+
+int launch_w3(const WgradCall& d, const WgradPlan& p, hipStream_t st) {
+  Wgrad2K k;
+  Wgrad3Out outs;
+  fill_problems(k, outs, d, p);
+  k.Cin = (d.Cin + 7) & ~7; k.Cout = (d.Cout + 7) & ~7;  // bounds of the 8-channel vector loads; the reduce kernel keeps the true counts
+  k.N = d.N; k.H = d.H; k.W = d.W; k.SEG = cdiv(d.W, 32);
+  k.Upair = (long long)d.N * d.H * k.SEG; k.U = k.Upair * d.npairs;
+#ifdef VMG_DIAG
+  { const char* e = getenv("VMG_WGRAD_DBG"); k.dbg = e ? atoi(e) : 0; }
+#endif
+  const bool b = p.kernel == last_kernel_id(VMG_WGRAD_3B);
+  if (b) {
+    allow_lds<conv_wgrad3b_kernel>(160 * 1024);
+    hipLaunchKernelGGL(conv_wgrad3b_kernel, dim3((unsigned)p.wgs), dim3(W3_THREADS), 6 * W3_BUF, st, k);
+  } else {
+    allow_lds<conv_wgrad3_kernel>(160 * 1024);
+    hipLaunchKernelGGL(conv_wgrad3_kernel, dim3((unsigned)p.wgs), dim3(W3_THREADS), 6 * W3_BUF, st, k);
+  }
+  VMG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(conv_wgrad3_reduce_kernel, dim3(p.rblocks, d.nprob), dim3(256), 0, st, (const float*)d.ws, p.S, p.gx, p.gy, d.Cin, d.Cout, outs, d.I_total, d.o0, d.i0,
+                     b ? 1 : 0 /* conv_wgrad3b_kernel keeps the bias sums in the padding tile */);
+  VMG_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_l2(const WgradCall& d, const WgradPlan& p, hipStream_t st) {
+  Lgrad2K k;
+  Wgrad3Out outs;
+  fill_problems(k, outs, d, p);
+  k.Cin = d.Cin; k.Cout = d.Cout;
+  k.Mpair = d.M;
+  k.Upair = (k.Mpair + 31) / 32; k.U = k.Upair * d.npairs;
+  hipLaunchKernelGGL(linear_wgrad2_kernel, dim3((unsigned)p.wgs), dim3(W2_THREADS), 3 * L2_BUF, st, k);
+  VMG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(linear_wgrad2_reduce_kernel, dim3(p.rblocks, d.nprob), dim3(256), 0, st, (const float*)d.ws, p.S, p.gx, p.gy, d.Cin, d.Cout, outs, d.I_total, d.o0, d.i0);
+  VMG_LAUNCH_CHECK();
+  return 0;
+}
+
+int wgrad_launch(const WgradCall& d, const WgradPlan& p, int facts, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  g_last_kernel = p.kernel;
+  const bool bf = d.dtype == VMG_BF16;
+  switch (p.kernel) {
+    case last_kernel_id(VMG_WGRAD_L2): return launch_l2(d, p, st);
+    case last_kernel_id(VMG_WGRAD_3):
+    case last_kernel_id(VMG_WGRAD_3B): return launch_w3(d, p, st);
+    case last_kernel_id(VMG_WGRAD_7, 1, 3): return launch_w7<1, 3>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_7, 1, 7): return launch_w7<1, 7>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_7, 2, 7): return launch_w7<2, 7>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_7, 4, 7): return launch_w7<4, 7>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_V1, 7, 1, 1): return bf ? launch_v1<bf16, 7, 1, 1>(d, p, facts, st) : launch_v1<float, 7, 1, 1>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_V1, 3, 1, 4): return launch_v1<bf16, 3, 1, 4>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_V1, 3, 1, 1): return launch_v1<bf16, 3, 1, 1>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_V1, 3, 3, 1): return bf ? launch_v1<bf16, 3, 3, 1>(d, p, facts, st) : launch_v1<float, 3, 3, 1>(d, p, facts, st);
+    case last_kernel_id(VMG_WGRAD_V1, 1, 3, 3): return bf ? launch_v1<bf16, 1, 3, 3>(d, p, facts, st) : launch_v1<float, 1, 3, 3>(d, p, facts, st);
+  }
+  vmg_set_error("conv_wgrad: no kernel for plan %#x", p.kernel);
+  return -1;
+}
+
+int g_w3_variant = 1;  // 1: conv_wgrad3b_kernel (buffer-addressed copies between the MFMA columns), 0: conv_wgrad3_kernel
+
+int wgrad_run(const WgradCall& d, void* stream) {
+  const int facts = wgrad_pointer_facts(d);
+  if (wgrad_validate(d, facts)) return -1;
+  const WgradPlan p = wgrad_plan(d, g_w3_variant, facts);
+  VMG_CHECK(p.kernel, "conv_wgrad multi: not bf16 operands in aligned 8-channel vectors, too few pixels or too small a workspace for the large-tile kernel (use vmg_conv_wgrad_batched_ws)");
+  return wgrad_launch(d, p, facts, stream);
+}
+
 }  // namespace
 
-// Shared by the single and the multi-problem entry points.  Returns 1 when the workspace cannot hold the slabs (caller falls back).
-static int g_w3_variant = 1;  // 1: conv_wgrad3b_kernel (buffer-addressed copies between the MFMA columns), 0: conv_wgrad3_kernel
+extern "C" int vmg_conv_wgrad_last_kernel(void) { return g_last_kernel; }
+
 extern "C" int vmg_conv_wgrad3_variant(int v) {
   const int prev = g_w3_variant;
   if (v == 0 || v == 1) g_w3_variant = v;
   return prev;
 }
 
-static int launch_wgrad3(int nprob, int npairs, const void* const* x, const void* const* dy, int N, int H, int W, int64_t x_ps, int Cin, int64_t dy_ps,
-                         int Cout, float* const* dW, int I_total, int o0, int i0, float* const* db, const float* scales, void* ws, int64_t ws_bytes,
-                         void* stream) {
-  const int cin8 = (Cin + 7) & ~7, cout8 = (Cout + 7) & ~7;
-  Wgrad2K k;
-  memset(&k, 0, sizeof(k));
-  Wgrad3Out outs;
-  memset(&outs, 0, sizeof(outs));
-  bool any_bias = false;
-  for (int q = 0; q < nprob; ++q) {
-    for (int p = 0; p < npairs; ++p) {
-      k.x[q * WG_MAX_PAIRS + p] = (const char*)x[q * npairs + p];
-      k.dy[q * WG_MAX_PAIRS + p] = (const char*)dy[q * npairs + p];
-    }
-    outs.dW[q] = dW[q];
-    outs.db[q] = db ? db[q] : nullptr;
-    outs.scale[q] = scales[q];
-    any_bias = any_bias || outs.db[q] != nullptr;
-  }
-  k.npairs = npairs; k.nprob = nprob; k.x_ps = x_ps; k.dy_ps = dy_ps; k.Cin = cin8; k.Cout = cout8;  // bounds of the 8-channel vector loads; the reduce kernel keeps the true counts
-  k.N = N; k.H = H; k.W = W; k.SEG = cdiv(W, 32);
-  k.Upair = (long long)N * H * k.SEG; k.U = k.Upair * npairs;
-  k.has_bias = any_bias;
-  const int gx = cdiv(Cout, W2_DYC), gy = cdiv(Cin, W2_XC);
-  long long S = 256 / ((long long)gx * gy * nprob);  // one workgroup per CU over all problems
-  if (S > k.U / 8) S = k.U / 8;
-  if (S < 1) S = 1;
-  const long long need = (long long)nprob * S * gx * gy * W3_WG_FLOATS * 4;
-  if (need > ws_bytes) return 1;
-  hipStream_t st = (hipStream_t)stream;
-  k.S = (int)S; k.slab = (float*)ws; k.gx = gx; k.gy = gy;
-#ifdef VMG_DIAG
-  { const char* e = getenv("VMG_WGRAD_DBG"); k.dbg = e ? atoi(e) : 0; }
-#endif
-  static bool attr3[VMG_MAX_DEVICES] = {};  // the attribute is per device
-  const int dev3 = vmg_current_device();
-  if (!attr3[dev3]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr3[dev3] = true;
-  }
-  // the buffer-addressed variant needs every byte of a pair's tensors (plus the X tile's reach of two rows and 34 pixels) below 2^31 from the base
-  int bias_in_pad = 0;
-  const long long reach = ((long long)N * H * W + 2LL * W + 40) * (x_ps > dy_ps ? x_ps : dy_ps) * 2;
-  if (g_w3_variant == 1 && reach < (1LL << 31)) {
-    static bool attr3b[VMG_MAX_DEVICES] = {};
-    if (!attr3b[dev3]) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad3b_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr3b[dev3] = true;
-    }
-    hipLaunchKernelGGL(conv_wgrad3b_kernel, dim3((unsigned)(gx * gy * S * nprob)), dim3(W3_THREADS), 6 * W3_BUF, st, k);
-    g_last_kernel = last_kernel_id(VMG_WGRAD_3B);
-    bias_in_pad = 1;
-  } else {
-    hipLaunchKernelGGL(conv_wgrad3_kernel, dim3((unsigned)(gx * gy * S * nprob)), dim3(W3_THREADS), 6 * W3_BUF, st, k);
-    g_last_kernel = last_kernel_id(VMG_WGRAD_3);
-  }
-  VMG_LAUNCH_CHECK();
-  const long long per3 = (long long)gy * gx * W3_WG_FLOATS;
-  const int rb3 = (int)(cdiv64(per3, 64) > 8192 ? 8192 : cdiv64(per3, 64));
-  hipLaunchKernelGGL(conv_wgrad3_reduce_kernel, dim3(rb3, nprob), dim3(256), 0, st, (const float*)ws, (int)S, gx, gy, Cin, Cout, outs, I_total, o0, i0, bias_in_pad);
-  VMG_LAUNCH_CHECK();
-  return 0;
-}
-
-// 1x1 / Linear weight gradients: one or several problems of one shape per launch.  Returns 1 when the large-tile path does not apply
-// (workspace too small, tiny problem): the caller falls back.
-static int launch_lgrad2(int nprob, int npairs, const void* const* x, const void* const* dy, long long Mpair, int64_t x_ps, int Cin, int64_t dy_ps,
-                         int Cout, float* const* dW, int I_total, int o0, int i0, float* const* db, const float* scales, void* ws,
-                         int64_t ws_bytes, void* stream) {
-  Lgrad2K k;
-  memset(&k, 0, sizeof(k));
-  Wgrad3Out outs;
-  memset(&outs, 0, sizeof(outs));
-  k.Mpair = Mpair;
-  k.Upair = (k.Mpair + 31) / 32; k.U = k.Upair * npairs;
-  const int gx = cdiv(Cout, 144), gy = cdiv(Cin, 144);
-  long long S = 512 / ((long long)gx * gy * nprob);  // two workgroups per CU over all problems
-  if (S > k.U / 8) S = k.U / 8;
-  if (S < 1) S = 1;
-  const long long need = (long long)nprob * S * gx * gy * L2_WG_FLOATS * 4;
-  if (need > ws_bytes || k.U < 64) return 1;  // (tiny problems: the v1 kernel's single launch is cheaper)
-  bool any_bias = false;
-  for (int q = 0; q < nprob; ++q) {
-    for (int p = 0; p < npairs; ++p) {
-      k.x[q * WG_MAX_PAIRS + p] = (const char*)x[q * npairs + p];
-      k.dy[q * WG_MAX_PAIRS + p] = (const char*)dy[q * npairs + p];
-    }
-    outs.dW[q] = dW[q];
-    outs.db[q] = db ? db[q] : nullptr;
-    outs.scale[q] = scales[q];
-    any_bias = any_bias || outs.db[q] != nullptr;
-  }
-  k.npairs = npairs; k.nprob = nprob; k.x_ps = x_ps; k.dy_ps = dy_ps; k.Cin = Cin; k.Cout = Cout; k.S = (int)S; k.slab = (float*)ws;
-  k.has_bias = any_bias;
-  k.gx = gx; k.gy = gy;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(linear_wgrad2_kernel, dim3((unsigned)(gx * gy * S * nprob)), dim3(W2_THREADS), 3 * L2_BUF, st, k);
-  g_last_kernel = last_kernel_id(VMG_WGRAD_L2);
-  VMG_LAUNCH_CHECK();
-  const long long per_s = (long long)gy * gx * L2_WG_FLOATS;
-  const int rb = (int)(cdiv64(per_s, 64) > 8192 ? 8192 : cdiv64(per_s, 64));
-  hipLaunchKernelGGL(linear_wgrad2_reduce_kernel, dim3(rb, nprob), dim3(256), 0, st, (const float*)ws, (int)S, gx, gy, Cin, Cout, outs, I_total, o0, i0);
-  VMG_LAUNCH_CHECK();
-  return 0;
-}
-
-// Several 1x1 / Linear weight gradients of ONE shape in one launch (the token mixers and projections of a TAB stage): x / dy hold
-// nprob * npairs pointers [problem][pair] over M pixels each, dW (O_total, I_total) / db one pointer and scales one factor per problem.
-extern "C" int vmg_linear_wgrad2_multi(int nprob, int npairs, const void* const* x, const void* const* dy, int64_t M, int64_t x_ps, int Cin,
-                                       int64_t dy_ps, int Cout, float* const* dW, int I_total, int o0, int i0, float* const* db,
-                                       const float* scales, void* ws, int64_t ws_bytes, void* stream) {
-  VMG_CHECK(nprob >= 1 && nprob <= W3_MAX_PROBS && npairs >= 1 && npairs <= WG_MAX_PAIRS && x && dy && dW && ws && scales, "linear_wgrad2_multi: 1..%d problems, 1..%d pairs",
-            W3_MAX_PROBS, WG_MAX_PAIRS);
-  VMG_CHECK(M > 0 && (x_ps % 8 == 0) && (dy_ps % 8 == 0) && (Cin % 8 == 0) && (Cout % 8 == 0) && x_ps >= Cin && dy_ps >= Cout && i0 >= 0 && i0 + Cin <= I_total && o0 >= 0,
-            "linear_wgrad2_multi: bf16 with 8-channel vectors only");
-  for (int p = 0; p < nprob * npairs; ++p)
-    VMG_CHECK(x[p] && dy[p] && ((uintptr_t)x[p] % 16 == 0) && ((uintptr_t)dy[p] % 16 == 0), "linear_wgrad2_multi: null or unaligned pointer %d", p);
-  for (int p = 0; p < nprob; ++p) VMG_CHECK(dW[p], "linear_wgrad2_multi: null gradient pointer %d", p);
-  const int rc = launch_lgrad2(nprob, npairs, x, dy, M, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scales, ws, ws_bytes, stream);
-  VMG_CHECK(rc != 1, "linear_wgrad2_multi: problem too small for the large-tile kernel or workspace too small (use vmg_conv_wgrad_batched_ws)");
-  return rc;
-}
-
 extern "C" int64_t vmg_conv_wgrad_ws_bytes(void) { return 320LL * W3_WG_FLOATS * 4; }  // up to 320 workgroups of slabs (~94 MB)
+
+extern "C" int vmg_conv_wgrad_plan(int entry, int dtype, int ks, int nprob, int npairs, int N, int H, int W, int64_t x_ps, int Cin, int64_t dy_ps, int Cout,
+                                   int I_total, int o0, int i0, int align, int64_t ws_bytes, int* plan) {
+  VMG_CHECK(entry >= VMG_WGRAD_ENTRY_PLAIN && entry <= VMG_WGRAD_ENTRY_MULTI && plan, "conv_wgrad_plan: bad entry or null plan");
+  const WgradCall d = {entry, dtype, ks, nprob, npairs, nullptr, nullptr, N, H, W, pixels(N, H, W), x_ps, dy_ps, Cin, Cout, nullptr, nullptr, nullptr, I_total, o0, i0,
+                       nullptr, ws_bytes > 0 ? ws_bytes : 0};
+  const int facts = align & (VMG_WGRAD_ALIGN_X16 | VMG_WGRAD_ALIGN_DY16 | VMG_WGRAD_ALIGN_DY2);
+  if (wgrad_validate(d, facts)) return -1;
+  const WgradPlan p = wgrad_plan(d, g_w3_variant, facts);
+  const int out[VMG_WGRAD_PLAN_INTS] = {p.kernel, p.gx, p.gy, p.S, (int)p.wgs, p.slabs, p.rblocks};
+  memcpy(plan, out, sizeof(out));
+  return 0;
+}
+
+extern "C" int vmg_conv_wgrad(int dtype, int ks, int N, int H, int W, const void* x, int64_t x_ps, int Cin, const void* dy,
+                              int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0, float* db, float scale,
+                              void* stream) {
+  return vmg_conv_wgrad_batched(dtype, ks, 1, &x, &dy, N, H, W, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scale, stream);
+}
+
+extern "C" int vmg_conv_wgrad_batched(int dtype, int ks, int npairs, const void* const* x, const void* const* dy, int N, int H, int W,
+                                      int64_t x_ps, int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0,
+                                      float* db, float scale, void* stream) {
+  const WgradCall d = {VMG_WGRAD_ENTRY_PLAIN, dtype, ks, 1, npairs, x, dy, N, H, W, pixels(N, H, W), x_ps, dy_ps, Cin, Cout, &dW, &db, &scale, I_total, o0, i0,
+                       nullptr, 0};
+  return wgrad_run(d, stream);
+}
 
 extern "C" int vmg_conv_wgrad_batched_ws(int dtype, int ks, int npairs, const void* const* x, const void* const* dy, int N, int H, int W,
                                          int64_t x_ps, int Cin, int64_t dy_ps, int Cout, float* dW, int I_total, int o0, int i0,
                                          float* db, float scale, void* ws, int64_t ws_bytes, void* stream) {
-  if (ws && dtype == VMG_BF16 && ks == 1 && npairs >= 1 && npairs <= WG_MAX_PAIRS && x && dy && dW && (x_ps % 8 == 0) && (dy_ps % 8 == 0) &&
-      (Cin % 8 == 0) && (Cout % 8 == 0) && x_ps >= Cin && dy_ps >= Cout && N > 0 && H > 0 && W > 0 && i0 >= 0 && i0 + Cin <= I_total && o0 >= 0) {
-    bool al = true;
-    for (int p = 0; al && p < npairs; ++p) al = x[p] && dy[p] && ((uintptr_t)x[p] % 16 == 0) && ((uintptr_t)dy[p] % 16 == 0);
-    if (al) {
-      const int rc = launch_lgrad2(1, npairs, x, dy, (long long)N * H * W, x_ps, Cin, dy_ps, Cout, &dW, I_total, o0, i0, &db, &scale, ws, ws_bytes, stream);
-      if (rc <= 0) return rc;
-    }
-  }
-  // 7x7 with <= 64 output channels and 3x3 with <= 16: one wave per tap row (conv_wgrad7_kernel)
-  const int rows_u = ks == 7 ? W7Geo<7>::R : W7Geo<3>::R;
-  if (ws && dtype == VMG_BF16 && ((ks == 7 && Cout <= 64) || (ks == 3 && Cout <= 16)) && npairs >= 1 && npairs <= WG_MAX_PAIRS && x && dy && dW &&
-      (x_ps % 8 == 0) && (Cin % 8 == 0) && x_ps >= Cin && dy_ps >= Cout && N > 0 && H > 0 && W > 0 && i0 >= 0 && i0 + Cin <= I_total && o0 >= 0 &&
-      (long long)npairs * N * cdiv(H, rows_u) * cdiv(W, 32) < (1LL << 30)) {
-    bool al = true, vdy = (dy_ps % 8 == 0);  // (channels past Cout inside the last vector are computed and dropped)
-    for (int p = 0; al && p < npairs; ++p) {
-      al = x[p] && dy[p] && ((uintptr_t)x[p] % 16 == 0) && ((uintptr_t)dy[p] % 2 == 0);
-      vdy = vdy && ((uintptr_t)dy[p] % 16 == 0);
-    }
-    if (al) {
-      Wgrad7K k;
-      memset(&k, 0, sizeof(k));
-      for (int p = 0; p < npairs; ++p) { k.x[p] = (const char*)x[p]; k.dy[p] = (const char*)dy[p]; }
-      k.npairs = npairs; k.x_ps = x_ps; k.dy_ps = dy_ps; k.Cin = Cin; k.Cout = Cout; k.vec_dy = vdy ? 1 : 0; k.slab = (float*)ws;
-      k.N = N; k.H = H; k.W = W; k.SEG = cdiv(W, 32); k.HB = cdiv(H, rows_u);
-      k.Upair = N * k.HB * k.SEG; k.U = k.Upair * npairs;
-      k.has_bias = db != nullptr;
-      hipStream_t st = (hipStream_t)stream;
-      const int ct = cdiv(Cout, 16);
-      const int rc = ks == 3   ? launch_wgrad7<1, 3>(k, dW, I_total, o0, i0, db, scale, ws_bytes, st)
-                     : ct == 1 ? launch_wgrad7<1>(k, dW, I_total, o0, i0, db, scale, ws_bytes, st)
-                     : ct == 2 ? launch_wgrad7<2>(k, dW, I_total, o0, i0, db, scale, ws_bytes, st)
-                               : launch_wgrad7<4>(k, dW, I_total, o0, i0, db, scale, ws_bytes, st);
-      if (rc <= 0) return rc;
-    }
-  }
-  // the large-tile path needs bf16, 3x3, 16-byte aligned 8-channel vectors; anything else takes the v1 kernel
-  // (a channel count that is not a multiple of 8 is fine when the pixel stride has room for the whole last vector -- the
-  // zero-padded input of the 3-channel stem conv, a slice of a wider tensor: the extra channels are computed and dropped)
-  const int cin8 = (Cin + 7) & ~7, cout8 = (Cout + 7) & ~7;
-  bool ok = ws && dtype == VMG_BF16 && ks == 3 && npairs >= 1 && npairs <= WG_MAX_PAIRS && x && dy && (x_ps % 8 == 0) && (dy_ps % 8 == 0) &&
-            x_ps >= cin8 && dy_ps >= cout8 && Cout > 16;  // (Cout <= 16: the 144-channel tile would be 9/10 padding; the 16-channel tile of the v1 kernel)
-  for (int p = 0; ok && p < npairs; ++p) ok = x[p] && dy[p] && ((uintptr_t)x[p] % 16 == 0) && ((uintptr_t)dy[p] % 16 == 0);
-  if (!ok) return wgrad_impl(dtype, ks, npairs, x, dy, N, H, W, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scale, stream, (float*)ws, ws_bytes);
-  VMG_CHECK(N > 0 && H > 0 && W > 0 && dW && x_ps >= Cin && dy_ps >= Cout && i0 >= 0 && i0 + Cin <= I_total && o0 >= 0, "conv_wgrad: bad arguments");
-  const int rc = launch_wgrad3(1, npairs, x, dy, N, H, W, x_ps, Cin, dy_ps, Cout, &dW, I_total, o0, i0, &db, &scale, ws, ws_bytes, stream);
-  if (rc == 1) return wgrad_impl(dtype, ks, npairs, x, dy, N, H, W, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scale, stream);
-  return rc;
+  const WgradCall d = {VMG_WGRAD_ENTRY_WS, dtype, ks, 1, npairs, x, dy, N, H, W, pixels(N, H, W), x_ps, dy_ps, Cin, Cout, &dW, &db, &scale, I_total, o0, i0,
+                       ws, ws && ws_bytes > 0 ? ws_bytes : 0};
+  return wgrad_run(d, stream);
 }
 
 // Several weight gradients of ONE shape (the 30 equal convs of a recurrent residual chain all complete at the same moment of the
@@ -1598,15 +1613,17 @@ extern "C" int vmg_conv_wgrad_batched_ws(int dtype, int ks, int npairs, const vo
 extern "C" int vmg_conv_wgrad3_multi(int nprob, int npairs, const void* const* x, const void* const* dy, int N, int H, int W, int64_t x_ps, int Cin,
                                      int64_t dy_ps, int Cout, float* const* dW, int I_total, int o0, int i0, float* const* db, const float* scales,
                                      void* ws, int64_t ws_bytes, void* stream) {
-  VMG_CHECK(nprob >= 1 && nprob <= W3_MAX_PROBS && npairs >= 1 && npairs <= WG_MAX_PAIRS && x && dy && dW && ws && scales, "conv_wgrad3_multi: 1..%d problems, 1..%d pairs",
-            W3_MAX_PROBS, WG_MAX_PAIRS);
-  const int cin8 = (Cin + 7) & ~7, cout8 = (Cout + 7) & ~7;
-  VMG_CHECK(N > 0 && H > 0 && W > 0 && (x_ps % 8 == 0) && (dy_ps % 8 == 0) && x_ps >= cin8 && dy_ps >= cout8 && i0 >= 0 && i0 + Cin <= I_total && o0 >= 0,
-            "conv_wgrad3_multi: bf16 3x3 with 8-channel vectors only");
-  for (int p = 0; p < nprob * npairs; ++p)
-    VMG_CHECK(x[p] && dy[p] && ((uintptr_t)x[p] % 16 == 0) && ((uintptr_t)dy[p] % 16 == 0), "conv_wgrad3_multi: null or unaligned pointer %d", p);
-  for (int p = 0; p < nprob; ++p) VMG_CHECK(dW[p], "conv_wgrad3_multi: null gradient pointer %d", p);
-  const int rc = launch_wgrad3(nprob, npairs, x, dy, N, H, W, x_ps, Cin, dy_ps, Cout, dW, I_total, o0, i0, db, scales, ws, ws_bytes, stream);
-  VMG_CHECK(rc != 1, "conv_wgrad3_multi: the workspace is too small");
-  return rc;
+  const WgradCall d = {VMG_WGRAD_ENTRY_MULTI, VMG_BF16, 3, nprob, npairs, x, dy, N, H, W, pixels(N, H, W), x_ps, dy_ps, Cin, Cout, dW, db, scales, I_total, o0, i0,
+                       ws, ws_bytes > 0 ? ws_bytes : 0};
+  return wgrad_run(d, stream);
+}
+
+// Several 1x1 / Linear weight gradients of ONE shape in one launch (the token mixers and projections of a TAB stage): x / dy hold
+// nprob * npairs pointers [problem][pair] over M pixels each, dW (O_total, I_total) / db one pointer and scales one factor per problem.
+extern "C" int vmg_linear_wgrad2_multi(int nprob, int npairs, const void* const* x, const void* const* dy, int64_t M, int64_t x_ps, int Cin,
+                                       int64_t dy_ps, int Cout, float* const* dW, int I_total, int o0, int i0, float* const* db,
+                                       const float* scales, void* ws, int64_t ws_bytes, void* stream) {
+  const WgradCall d = {VMG_WGRAD_ENTRY_MULTI, VMG_BF16, 1, nprob, npairs, x, dy, 0, 0, 0, M, x_ps, dy_ps, Cin, Cout, dW, db, scales, I_total, o0, i0,
+                       ws, ws_bytes > 0 ? ws_bytes : 0};
+  return wgrad_run(d, stream);
 }

@@ -120,6 +120,8 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "vmg_conv_wgrad3_variant": (c_int, [c_int]),
     "vmg_conv_wgrad_last_kernel": (c_int, []),
+    "vmg_conv_wgrad_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64,
+                                    POINTER(c_int)]),
     "vmg_win3d_variant": (c_int, [c_int]),
     "vmg_linear_wgrad2_multi": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

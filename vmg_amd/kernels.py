@@ -308,25 +308,38 @@ def resblock_chain_backward(g: torch.Tensor, ts: Sequence[torch.Tensor], pd1: Se
     return gys, gts
 
 
+def _wgrad_operands(name: str, xs, dys, dW: torch.Tensor, db: Optional[torch.Tensor], ks: int, M: int, o0: int = 0, i0: int = 0, like=None,
+                    whole: bool = False):
+    """The operand checks of conv_wgrad, conv_wgrad_batched and the multi wrappers, for one problem: fp32 contiguous gradients; every
+    (x, dy) pair of one dtype, channel counts and pixel strides (those of the pair `like`, else of the first pair) over M pixels; dW / db
+    matching (ks, Cout + o0, Cin + i0) -- whole: the call covers the whole parameter (3x3: all output channels).
+    Returns (Cin, Cout, x_ps, dy_ps, I_total)."""
+    hip.require_cuda(dW, db, *xs, *dys)
+    if dW.dtype != torch.float32 or not dW.is_contiguous() or (db is not None and (db.dtype != torch.float32 or not db.is_contiguous())):
+        raise HipError(f"{name}: parameter gradients must be contiguous fp32")
+    x0, d0 = like or (xs[0], dys[0])
+    Cin, Cout = x0.shape[-1], d0.shape[-1]
+    xps, dps = _pix_stride(x0), _pix_stride(d0)
+    for x, d in zip(xs, dys):
+        if x.dtype != x0.dtype or d.dtype != x0.dtype or x.shape[-1] != Cin or d.shape[-1] != Cout or x.numel() // Cin != M or \
+                d.numel() // Cout != M or _pix_stride(x) != xps or _pix_stride(d) != dps:
+            raise HipError(f"{name}: all pairs must share dtype, shape and strides and cover the N*H*W pixels")
+    O_total, I_total = dW.shape[0], dW.shape[1]
+    kk = 1 if dW.dim() == 2 else dW.shape[2]
+    fits = kk == ks and o0 + Cout <= O_total and i0 + Cin <= I_total and (db is None or db.numel() == O_total)
+    if whole:  # (3x3: a group of a grouped convolution takes Cin of the weight's I_total input channels)
+        fits = fits and O_total == Cout and (dW.dim() == 4 if ks == 3 else (I_total == Cin and dW.numel() == Cout * Cin))
+    if not fits:
+        raise HipError(f"{name}: gradient tensor {tuple(dW.shape)} does not match conv (ks={ks}, Cout={Cout}+{o0}, Cin={Cin}+{i0})")
+    return Cin, Cout, xps, dps, I_total
+
+
 def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, dW: torch.Tensor, db: Optional[torch.Tensor], ks: int, N: int, H: int,
                W: int, scale: float = 1.0, o0: int = 0, i0: int = 0):
     """dW (fp32, (O_total, I_total, ks, ks) or (O_total, I_total)) += scale * wgrad(x, dy); db += scale * sum(dy).
     x (..., Cin) and dy (..., Cout) are channels-last tensors over the same N*H*W pixels (channel slices allowed)."""
-    hip.require_cuda(x, dy, dW, db)
-    if dW.dtype != torch.float32 or not dW.is_contiguous() or (db is not None and (db.dtype != torch.float32 or not db.is_contiguous())):
-        raise HipError("parameter gradients must be contiguous fp32")
-    if x.dtype != dy.dtype:
-        raise HipError("x and dy must share a dtype")
-    M = N * H * W
-    Cin, Cout = x.shape[-1], dy.shape[-1]
-    if x.numel() // Cin != M or dy.numel() // Cout != M:
-        raise HipError("x / dy do not cover N*H*W pixels")
-    O_total, I_total = dW.shape[0], dW.shape[1]
-    kk = 1 if dW.dim() == 2 else dW.shape[2]
-    if kk != ks or o0 + Cout > O_total or i0 + Cin > I_total or (db is not None and db.numel() != O_total):
-        raise HipError(f"gradient tensor {tuple(dW.shape)} does not match conv (ks={ks}, Cout={Cout}+{o0}, Cin={Cin}+{i0})")
-    hip.check(hip.lib().vmg_conv_wgrad(hip.dtype_code(x.dtype), ks, N, H, W, x.data_ptr(), _pix_stride(x), Cin, dy.data_ptr(),
-                                       _pix_stride(dy), Cout, dW.data_ptr(), I_total, o0, i0,
+    Cin, Cout, xps, dps, I_total = _wgrad_operands("conv_wgrad", [x], [dy], dW, db, ks, N * H * W, o0, i0)
+    hip.check(hip.lib().vmg_conv_wgrad(hip.dtype_code(x.dtype), ks, N, H, W, x.data_ptr(), xps, Cin, dy.data_ptr(), dps, Cout, dW.data_ptr(), I_total, o0, i0,
                                        db.data_ptr() if db is not None else None, scale, hip.stream_ptr()), "vmg_conv_wgrad")
 
 
@@ -818,22 +831,8 @@ def conv_wgrad_batched(xs: Sequence[torch.Tensor], dys: Sequence[torch.Tensor], 
     """dW += scale * sum_p wgrad(xs[p], dys[p]) in as few launches as possible (16 pairs per launch)."""
     if len(xs) != len(dys) or not xs:
         raise HipError("conv_wgrad_batched: need equally many x and dy tensors")
-    x0, d0 = xs[0], dys[0]
-    hip.require_cuda(dW, db, *xs, *dys)
-    if dW.dtype != torch.float32 or not dW.is_contiguous() or (db is not None and (db.dtype != torch.float32 or not db.is_contiguous())):
-        raise HipError("parameter gradients must be contiguous fp32")
-    M = N * H * W
-    Cin, Cout = x0.shape[-1], d0.shape[-1]
-    xps, dps = _pix_stride(x0), _pix_stride(d0)
-    for x, d in zip(xs, dys):
-        if x.dtype != x0.dtype or d.dtype != x0.dtype or x.shape[-1] != Cin or d.shape[-1] != Cout or x.numel() // Cin != M or \
-                d.numel() // Cout != M or _pix_stride(x) != xps or _pix_stride(d) != dps:
-            raise HipError("conv_wgrad_batched: all pairs must share shape, dtype and strides")
-    O_total, I_total = dW.shape[0], dW.shape[1]
-    kk = 1 if dW.dim() == 2 else dW.shape[2]
-    if kk != ks or o0 + Cout > O_total or i0 + Cin > I_total or (db is not None and db.numel() != O_total):
-        raise HipError(f"gradient tensor {tuple(dW.shape)} does not match conv (ks={ks}, Cout={Cout}+{o0}, Cin={Cin}+{i0})")
-    code = hip.dtype_code(x0.dtype)
+    Cin, Cout, xps, dps, I_total = _wgrad_operands("conv_wgrad_batched", xs, dys, dW, db, ks, N * H * W, o0, i0)
+    code = hip.dtype_code(xs[0].dtype)
     l = hip.lib()
     ws = _workspace("vmg_conv_wgrad_ws_bytes", dW.device)
     for s in range(0, len(xs), 16):
@@ -846,12 +845,18 @@ def conv_wgrad_batched(xs: Sequence[torch.Tensor], dys: Sequence[torch.Tensor], 
 
 
 def conv_wgrad3_multi_ok(x: torch.Tensor, dy: torch.Tensor, ks: int) -> bool:
-    """Shapes vmg_conv_wgrad3_multi / vmg_linear_wgrad2_multi take: bf16, 3x3 or 1x1, pixel strides that are multiples of 8 channels, 16-byte
-    aligned tensors (1x1: channel counts multiples of 8 and at least 2 048 pixels)."""
-    if ks == 1 and (x.shape[-1] % 8 or dy.shape[-1] % 8 or x.numel() // x.shape[-1] < 2048):
+    """Operands vmg_conv_wgrad3_multi (ks 3) / vmg_linear_wgrad2_multi (ks 1) take: bf16, 16-byte aligned, pixel strides multiples of 8
+    channels; 3x3: strides no smaller than the channel counts rounded up to 8; 1x1: channel counts multiples of 8 and at least 2 048 pixels.
+    (The conditions of vmg_conv_wgrad_plan for the multi entries, restated here: this runs per parameter on the autograd thread.)"""
+    if ks not in (1, 3) or x.dtype != torch.bfloat16 or dy.dtype != torch.bfloat16 or x.data_ptr() % 16 or dy.data_ptr() % 16:
         return False
-    return (ks in (1, 3) and x.dtype == torch.bfloat16 and dy.dtype == torch.bfloat16 and x.stride(-1) == 1 and dy.stride(-1) == 1 and
-            x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
+    try:
+        strides = ((_pix_stride(x), x.shape[-1]), (_pix_stride(dy), dy.shape[-1]))
+    except HipError:  # (not a dense pixel array: conv_wgrad_batched says so)
+        return False
+    if ks == 1:
+        return all(ps % 8 == 0 and c % 8 == 0 for ps, c in strides) and x.numel() // x.shape[-1] >= 2048
+    return all(ps % 8 == 0 and ps >= (c + 7) // 8 * 8 for ps, c in strides)
 
 
 def _wgrad_multi(name: str, probs, dims: Sequence[int]):
@@ -861,22 +866,10 @@ def _wgrad_multi(name: str, probs, dims: Sequence[int]):
     M = dims[0] * dims[1] * dims[2] if conv3 else dims[0]
     xs0, dys0, dW0 = probs[0][:3]
     npairs = len(xs0)
-    Cin, Cout = xs0[0].shape[-1], dys0[0].shape[-1]
-    xps, dps = _pix_stride(xs0[0]), _pix_stride(dys0[0])
-    I_total = dW0.shape[1]
     for xs, dys, dW, db, _ in probs:
-        hip.require_cuda(dW, db, *xs, *dys)
-        if len(xs) != npairs or len(dys) != npairs or dW.shape != dW0.shape or dW.dtype != torch.float32 or not dW.is_contiguous() or \
-                (db is not None and (db.dtype != torch.float32 or not db.is_contiguous() or db.numel() != dW.shape[0])):
-            raise HipError(f"{name}: problems must share the shape; gradients contiguous fp32")
-        for x, d in zip(xs, dys):
-            if x.dtype != torch.bfloat16 or d.dtype != torch.bfloat16 or x.shape[-1] != Cin or d.shape[-1] != Cout or x.numel() // Cin != M or \
-                    d.numel() // Cout != M or _pix_stride(x) != xps or _pix_stride(d) != dps:
-                raise HipError(f"{name}: all pairs must share shape, dtype and strides")
-    # (3x3: a group of a grouped convolution takes Cin of the weight's I_total input channels)
-    fits = (dW0.dim() == 4 and dW0.shape[2] == 3 and Cin <= I_total) if conv3 else (Cin == I_total and dW0.numel() == Cout * Cin)
-    if dW0.shape[0] != Cout or not fits:
-        raise HipError(f"{name}: gradient tensor does not match the " + ("convolution" if conv3 else "layer"))
+        if len(xs) != npairs or len(dys) != npairs or dW.shape != dW0.shape or xs[0].dtype != torch.bfloat16:
+            raise HipError(f"{name}: problems must share the shape; operands bf16")
+        Cin, Cout, xps, dps, I_total = _wgrad_operands(name, xs, dys, dW, db, 3 if conv3 else 1, M, like=(xs0[0], dys0[0]), whole=True)
     entry = getattr(hip.lib(), "vmg_" + name)
     ws = _workspace("vmg_conv_wgrad_ws_bytes", dW0.device)
     for s in range(0, len(probs), 8):
