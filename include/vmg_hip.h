@@ -492,6 +492,28 @@ int vmg_spy_flow_add(int dtype, const float* up, const void* res, float* out, in
 /* vmg_spy_prep: SPyNet's input normalisation (models/vmg.py:104-106): img (n, 3, h, w) fp32, mean / std (3) fp32 on the device -> out (n, h, w, 8) in `dtype`,
  * channels 0..2 = (img - mean) / std, zeros behind. */
 int vmg_spy_prep(int dtype, const float* img, const float* mean, const float* stdv, void* out, int64_t n, int h, int w, void* stream);
+/* vmg_spy_module_fwd / _bwd: one SPyNetBasicModule (:126-173; 7x7 convolutions 8 -> 32 -> 64 -> 32 -> 16 -> 2, ReLU after the first four) on a coarse
+ * pyramid level as ONE launch per direction: bf16, one workgroup per image, H * W <= 256 and (H + 6) * (W + 6) <= 484 (the level's image
+ * with its 3-pixel zero border stays in LDS between the convolutions).  All tensors (N, H, W, C) channels-last, contiguous.
+ * packed[i]: conv i's vmg_conv_pack image with the default cout_tiles of the 7x7 route (2, 4, 2, 1, 1 forward; 1, 2, 4, 2, 1 for the
+ * data-gradient packs of conv0..conv4; conv4's data-gradient pack has K = 2 padded to 8).
+ *   fwd: x = the 8-channel operand; out = the flow residual (N, H, W, 2); y[0..3] = the four activated intermediates (all given: written
+ *        for the backward and the weight gradients; all null: inference); bias[0..4] fp32.
+ *   bwd: x = dpre4 = the residual's gradient zero-padded to 8 channels; y[0..3] as written by fwd; dpre[i] = dgrad_(i+1)(dpre_(i+1)) * relu'(y_i)
+ *        for i = 3..0 (outputs: the operands of vmg_conv_wgrad*); out = dx = dgrad_0(dpre0) (N, H, W, 8), or null: not wanted.
+ * Per output element the k-steps, their order, the point where bias enters and every bf16 rounding are those of vmg_conv_fwd (ks = 7) on the
+ * same packs: both routes give the same bits. */
+typedef struct vmg_spy_module_desc {
+  int N, H, W;
+  const void* x;
+  const void* packed[5];
+  const float* bias[5]; /* fwd only */
+  void* y[4];
+  void* out;
+  void* dpre[4]; /* bwd only */
+} vmg_spy_module_desc;
+int vmg_spy_module_fwd(const vmg_spy_module_desc* d, void* stream);
+int vmg_spy_module_bwd(const vmg_spy_module_desc* d, void* stream);
 
 /* ---- sliding-window inference accumulators (reference: tools/Tester.py:107-177, :249-250) --------------------------
  * vmg_tile_accumulate: for a tile `patch` (planes, ph, pw; dtype 0 = f32, 1 = bf16) placed at (oh, ow) of the fp32

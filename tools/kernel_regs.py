@@ -23,19 +23,18 @@ with tempfile.TemporaryDirectory() as td:
             continue
         notes = subprocess.run([f"{llvm}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
         cur = {}
-        for line in notes.splitlines() + ["- .name: end"]:
+        keys = (".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+        for line in notes.splitlines() + [".agpr_count: end"]:  # a kernel's record runs from its .agpr_count (keys are sorted) to the next one
             line = line.strip().lstrip("- ").strip()
-            if line.startswith(".name:") or line.startswith("- .name:"):
-                pass
-            if ":" in line:
-                k, v = line.split(":", 1)
-                k = k.strip().lstrip("-").strip()
-                if k == ".agpr_count" and cur.get(".name") and pat in cur.get(".name", ""):
-                    pass
-                if k in (".name", ".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size", ".symbol"):
-                    if k == ".symbol":
-                        if pat in cur.get(".name", ""):
-                            print(cur.get(".name", "?")[:110], {x: cur.get(x) for x in (".vgpr_count", ".agpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")})
-                        cur = {}
-                    else:
-                        cur[k] = v.strip()
+            if ":" not in line:
+                continue
+            k, v = line.split(":", 1)
+            k, v = k.strip(), v.strip()
+            if k == ".agpr_count":
+                if pat in cur.get(".name", ""):
+                    print(cur[".name"][:110], {x: cur.get(x) for x in keys})
+                cur = {k: v}
+            elif k in keys or (k == ".name" and ".symbol" not in cur and v.startswith("_Z")):
+                cur[k] = v
+            elif k == ".symbol":
+                cur[k] = v

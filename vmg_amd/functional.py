@@ -1378,6 +1378,59 @@ def spy_flow_add(up: torch.Tensor, res: torch.Tensor) -> torch.Tensor:
     return _SpyFlowAdd.apply(up, res)
 
 
+class _SpyModule(_Fn):
+    """One SPyNetBasicModule on a coarse pyramid level (bf16, h * w <= 256): the five 7x7 convolutions in ONE launch, their data gradients in
+    ONE more (K.spy_module_forward / _backward) -- this node stands where five _Conv2d nodes with fused ReLUs stand on the per-conv route, reads
+    the same packs, keeps the same intermediates and hands the weight gradients the same operands: both routes give the same bits."""
+
+    @staticmethod
+    def forward(ctx, x8, *wb):
+        ws, bs = wb[0::2], wb[1::2]
+        dt = x8.dtype
+        n, h, w, _ = x8.shape
+        ctx.want_dx = ctx.needs_input_grad[0]
+        ctx.want_w = [ctx.needs_input_grad[1 + 2 * i] for i in range(5)]
+        ctx.want_b = [ctx.needs_input_grad[2 + 2 * i] for i in range(5)]
+        keep = any(ctx.needs_input_grad)
+        packs = [packed(wt, dt, "fwd", [wt.shape[1]]) for wt in ws]
+        out, ys = K.spy_module_forward(x8.contiguous(), packs, bs, keep)
+        ctx.geo = (n, h, w)
+        if keep:
+            ctx.defer = [DEFERRED.defers(ws[i], bs[i], ctx.want_w[i]) for i in range(5)]
+            ctx.gen = [DEFERRED.note_use(ws[i], bs[i]) if ctx.defer[i] else 0 for i in range(5)]
+            ctx.bias_ref = bs
+            ctx.save_for_backward(x8, *ys, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        n, h, w = ctx.geo
+        saved = ctx.saved_tensors
+        x8, ys, ws = saved[0], saved[1:5], saved[5:10]
+        dpre4 = _pad_channels(dy.contiguous())  # (the data-gradient pack of the last convolution has K = 2 padded to 8, as on the per-conv route)
+        pds = [packed(wt, dy.dtype, "dgrad", None, 0, wt.shape[1]) for wt in ws]
+        dpre, dx = K.spy_module_backward(dpre4, pds, ys, ctx.want_dx)
+        dpre_w = list(dpre) + [dpre4[..., :2]]
+        grads = [None] * 10
+        for i in range(4, -1, -1):  # (the order in which the five _Conv2d nodes would run)
+            srcs, src_ch = [x8 if i == 0 else ys[i - 1]], [ws[i].shape[1]]
+            if ctx.defer[i]:
+                DEFERRED.add(ws[i], ctx.bias_ref[i], srcs, src_ch, dpre_w[i], 7, n, h, w, gen=ctx.gen[i])
+            elif ctx.want_w[i]:
+                grads[2 * i], grads[2 * i + 1] = _wgrad_now(ws[i], ctx.want_b[i], srcs, src_ch, dpre_w[i], 7, n, h, w)
+            elif ctx.want_b[i]:
+                grads[2 * i + 1] = dpre_w[i].float().reshape(-1, ws[i].shape[0]).sum(0)
+        return (dx, *grads)
+
+
+def spy_module(x8: torch.Tensor, convs) -> torch.Tensor:
+    """SPyNetBasicModule on the fused route: x8 (n,h,w,8) bf16, convs = its five nn.Conv2d parameter holders -> the flow residual (n,h,w,2)."""
+    wb = []
+    for c in convs:
+        wb += [c.weight, c.bias]
+    return _SpyModule.apply(x8, *wb)
+
+
 def identity_grid(n: int, h: int, w: int, device) -> torch.Tensor:
     ys, xs = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing="ij")
     return torch.stack([xs, ys], 0).float()[None].expand(n, -1, -1, -1).contiguous()

@@ -58,6 +58,14 @@ class ChainDesc(ctypes.Structure):
     ]
 
 
+class SpyModuleDesc(ctypes.Structure):
+    """vmg_spy_module_desc (include/vmg_hip.h)."""
+    _fields_ = [
+        ("N", c_int), ("H", c_int), ("W", c_int),
+        ("x", c_void_p), ("packed", c_void_p * 5), ("bias", c_void_p * 5), ("y", c_void_p * 4), ("out", c_void_p), ("dpre", c_void_p * 4),
+    ]
+
+
 class ConvQ8Desc(ctypes.Structure):
     """vmg_convq8_desc (include/vmg_hip.h)."""
     _fields_ = [
@@ -146,6 +154,8 @@ SIGNATURES = {
     "vmg_spy_operand_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "vmg_spy_flow_add": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "vmg_spy_prep": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "vmg_spy_module_fwd": (c_int, [POINTER(SpyModuleDesc), c_void_p]),
+    "vmg_spy_module_bwd": (c_int, [POINTER(SpyModuleDesc), c_void_p]),
     "vmg_space_depth_ln_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "vmg_space_depth_ln_bwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                        c_void_p, c_void_p]),

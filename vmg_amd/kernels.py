@@ -767,6 +767,68 @@ def spy_flow_add(up: torch.Tensor, res: torch.Tensor) -> torch.Tensor:
     return out
 
 
+SPY_CHANNELS = (8, 32, 64, 32, 16, 2)  # SPyNetBasicModule: conv i maps SPY_CHANNELS[i] -> SPY_CHANNELS[i + 1]
+SPY_FUSED_MAX_PIXELS = 256           # vmg_spy_module_*: h * w <= 256 and the image with its 3-pixel border <= 484 pixels (one LDS tile)
+SPY_FUSED_MAX_TILE = 484
+
+
+def _spy_module_check(name: str, x: torch.Tensor, packs: Sequence[PackedConv], dgrad: bool):
+    hip.require_cuda(x)
+    if x.dtype != torch.bfloat16 or x.dim() != 4 or x.shape[-1] != 8 or not x.is_contiguous():
+        raise HipError(f"{name}: contiguous bf16 (n, h, w, 8) operand expected, got {tuple(x.shape)} {x.dtype}")
+    n, h, w, _ = x.shape
+    if n < 1 or h * w > SPY_FUSED_MAX_PIXELS or (h + 6) * (w + 6) > SPY_FUSED_MAX_TILE:
+        raise HipError(f"{name}: a {h} x {w} level does not fit one workgroup's LDS")
+    if len(packs) != 5:
+        raise HipError(f"{name}: five packs expected")
+    for i, p in enumerate(packs):
+        cin, cout = SPY_CHANNELS[i], SPY_CHANNELS[i + 1]
+        k, o = ((cout + 7) // 8 * 8, cin) if dgrad else (cin, cout)
+        if p.layout != "std" or p.ks != 7 or p.dtype != torch.bfloat16 or p.src_ch != [k] or p.cout != o or p.cout_tiles != cout_tiles_for(o, p.dtype, 7):
+            raise HipError(f"{name}: pack {i} is not the 7x7 bf16 {'data-gradient ' if dgrad else ''}pack of a {cin} -> {cout} convolution")
+    return n, h, w
+
+
+def spy_module_forward(x8: torch.Tensor, packs: Sequence[PackedConv], biases: Sequence[torch.Tensor], keep: bool):
+    """One SPyNetBasicModule on a coarse level in one launch (vmg_spy_module_fwd): x8 (n,h,w,8) bf16, forward packs and biases of conv0..conv4
+    -> (residual (n,h,w,2), [y0..y3] when keep else None)."""
+    n, h, w = _spy_module_check("spy_module_forward", x8, packs, False)
+    hip.require_cuda(*biases)
+    if len(biases) != 5 or any(b.dtype != torch.float32 or b.numel() != SPY_CHANNELS[i + 1] or not b.is_contiguous() for i, b in enumerate(biases)):
+        raise HipError("spy_module_forward: five contiguous fp32 biases expected")
+    out = torch.empty((n, h, w, 2), dtype=x8.dtype, device=x8.device)
+    ys = [torch.empty((n, h, w, c), dtype=x8.dtype, device=x8.device) for c in SPY_CHANNELS[1:5]] if keep else None
+    d = hip.SpyModuleDesc()
+    d.N, d.H, d.W, d.x, d.out = n, h, w, x8.data_ptr(), out.data_ptr()
+    for i in range(5):
+        d.packed[i], d.bias[i] = packs[i].buf.data_ptr(), biases[i].data_ptr()
+    if keep:
+        for i in range(4):
+            d.y[i] = ys[i].data_ptr()
+    hip.check(hip.lib().vmg_spy_module_fwd(ctypes.byref(d), hip.stream_ptr()), "vmg_spy_module_fwd")
+    return out, ys
+
+
+def spy_module_backward(dpre4: torch.Tensor, packs: Sequence[PackedConv], ys: Sequence[torch.Tensor], want_dx: bool):
+    """The data-gradient sweep of spy_module_forward in one launch (vmg_spy_module_bwd): dpre4 (n,h,w,8) bf16 = the residual's gradient zero-padded
+    to 8 channels, data-gradient packs of conv0..conv4, ys as kept by the forward -> ([dpre0..dpre3], dx8 (n,h,w,8) or None)."""
+    n, h, w = _spy_module_check("spy_module_backward", dpre4, packs, True)
+    hip.require_cuda(*ys)
+    if len(ys) != 4 or any(y.dtype != dpre4.dtype or tuple(y.shape) != (n, h, w, SPY_CHANNELS[i + 1]) or not y.is_contiguous() for i, y in enumerate(ys)):
+        raise HipError("spy_module_backward: y0..y3 as written by spy_module_forward expected")
+    dpre = [torch.empty_like(y) for y in ys]
+    dx = torch.empty((n, h, w, 8), dtype=dpre4.dtype, device=dpre4.device) if want_dx else None
+    d = hip.SpyModuleDesc()
+    d.N, d.H, d.W, d.x = n, h, w, dpre4.data_ptr()
+    d.out = dx.data_ptr() if want_dx else None
+    for i in range(5):
+        d.packed[i] = packs[i].buf.data_ptr()
+    for i in range(4):
+        d.y[i], d.dpre[i] = ys[i].data_ptr(), dpre[i].data_ptr()
+    hip.check(hip.lib().vmg_spy_module_bwd(ctypes.byref(d), hip.stream_ptr()), "vmg_spy_module_bwd")
+    return dpre, dx
+
+
 def upsample2x_ac(x: torch.Tensor, scale: float, backward: bool = False) -> torch.Tensor:
     """forward: (n,h,w,c) fp32 -> scale * bilinear x2 (align_corners=True) (n,2h,2w,c); backward: the transpose on (n,2h,2w,c)."""
     hip.require_cuda(x)

@@ -16,6 +16,7 @@ There is no CPU path: calling the module on CPU tensors raises (vmg_amd.hip.HipE
 """
 from __future__ import annotations
 
+import os
 from fractions import Fraction
 from typing import List, Sequence
 
@@ -64,17 +65,35 @@ class _ConvModule(nn.Module):  # mmcv ConvModule naming: `.conv` holds the param
         self.act = act
 
 
+SPY_FUSED, SPY_PER_CONV = "fused", "per-conv"
+
+
+def spy_module_route(dtype, h: int, w: int, inner_dtype, src_channels: Sequence[int]) -> str:
+    """The kernels one SPyNetBasicModule call runs on.  SPY_FUSED: the whole module in one launch per direction (csrc/spy_module.hip) -- bf16, ONE
+    8-channel operand, no dtype change inside the module, and a level whose image with its 3-pixel border fits one workgroup's LDS tile
+    (h * w <= 256 and (h + 6) * (w + 6) <= 484: 1 x 1 .. 16 x 16, Vimeo's 8 x 14).  SPY_PER_CONV: five convolution launches (fp32, edge_fp32,
+    a virtual concat, larger levels).  Both give the same bits."""
+    from .kernels import SPY_FUSED_MAX_PIXELS, SPY_FUSED_MAX_TILE
+    fits = h >= 1 and w >= 1 and h * w <= SPY_FUSED_MAX_PIXELS and (h + 6) * (w + 6) <= SPY_FUSED_MAX_TILE
+    if dtype == torch.bfloat16 and inner_dtype is None and tuple(src_channels) == (8,) and fits:
+        return SPY_FUSED
+    return SPY_PER_CONV
+
+
 class SPyNetBasicModule(nn.Module):
     def __init__(self):
         super().__init__()
         self.basic_module = nn.Sequential(_ConvModule(8, 32, True), _ConvModule(32, 64, True), _ConvModule(64, 32, True),
                                           _ConvModule(32, 16, True), _ConvModule(16, 2, False))
 
-    def forward(self, srcs: Sequence[torch.Tensor], inner_dtype=None) -> torch.Tensor:
+    def forward(self, srcs: Sequence[torch.Tensor], inner_dtype=None, fused: bool = True) -> torch.Tensor:
         """srcs: channels-last tensors whose channels concatenate to the 8 input channels [ref, warped, flow] -> (n,h,w,2).
         inner_dtype: the three middle convolutions (32 -> 64 -> 32 -> 16, 94 % of the module's FLOPs) compute in this dtype while the first and
-        the last one -- the two that touch the flow -- keep the dtype of `srcs` (SPyNet.edge_fp32)."""
+        the last one -- the two that touch the flow -- keep the dtype of `srcs` (SPyNet.edge_fp32).
+        fused: False keeps every level on the per-conv route (SPyNet.fused_modules)."""
         n, h, w = srcs[0].shape[:3]
+        if fused and spy_module_route(srcs[0].dtype, h, w, inner_dtype, [s.shape[-1] for s in srcs]) == SPY_FUSED:
+            return FH.spy_module(srcs[0], [m.conv for m in self.basic_module])
         y = list(srcs)
         last = len(self.basic_module) - 1
         for i, m in enumerate(self.basic_module):
@@ -91,7 +110,6 @@ class SPyNet(nn.Module):
         super().__init__()
         self.basic_module = nn.ModuleList([SPyNetBasicModule() for _ in range(6)])
         if isinstance(pretrained, str):
-            import os
             if os.path.isfile(pretrained):
                 sd = torch.load(pretrained, map_location="cpu")
                 self.load_state_dict(sd.get("state_dict", sd), strict=True)
@@ -106,6 +124,9 @@ class SPyNet(nn.Module):
         # first convolution (8 -> 32: its data gradient IS the flow gradient of the level below) and the last one (16 -> 2: its output is the
         # flow residual, its output gradient the flow gradient) -- stays fp32; only the three middle convolutions run in bf16.
         self.edge_fp32 = False
+        # coarse levels (<= 16 x 16) run each basic module as one launch per direction (spy_module_route); False, or VMG_SPY_FUSED=0 in the
+        # environment, keeps every level on the per-conv route -- the same bits either way, for A/B timing
+        self.fused_modules = os.environ.get("VMG_SPY_FUSED", "1") != "0"
 
     def compute_flow(self, ref: torch.Tensor, supp: torch.Tensor) -> torch.Tensor:
         """ref, supp: channels-last (n,h,w,8) in the compute dtype, normalised RGB in channels 0..2 and zeros behind (the warp
@@ -129,7 +150,7 @@ class SPyNet(nn.Module):
             # one 8-channel operand [ref, warped, flow] (a 16-byte vector per pixel) instead of a virtual concat of 3 + 3 + 2 channels:
             # the convolution and its weight gradient then move whole vectors
             x8 = FH.spy_operand(refs[level], warped, up)
-            res = self.basic_module[level]([x8], inner)
+            res = self.basic_module[level]([x8], inner, self.fused_modules)
             flow = FH.spy_flow_add(up, res)
         return flow
 
@@ -545,6 +566,8 @@ class Mlp_encoder(nn.Module):
                  traj_scale, m_scaling, if_local_fuse, channel_mixer):
         super().__init__()
         self.aligned, self.empty = aligned, empty_aligned
+        self.takes_flows, self.keeps_flow_scale = self.flow_use(aligned, empty_aligned)
+        self._smooth_unused = False  # tests only (VMG._set_flows_all_scales)
         self.if_smooth, self.region_range = if_smooth, region_range
         self.local_fuse = if_local_fuse
         if if_local_fuse:
@@ -558,6 +581,17 @@ class Mlp_encoder(nn.Module):
             self.traj_mixing = nn.Identity() if empty_aligned else DecoderLayer(embed_dim, 2, segm, window_size, mlp_ratio, qkv_bias)
         else:
             self.traj_mixing = Trajectory_multi_head(embed_dim, traj_r_n, n_nonkeyframes, traj_heads, traj_scale, r_scaling, twins)
+
+    @staticmethod
+    def flow_use(aligned, empty_aligned):
+        """(takes_flows, keeps_flow_scale) of a stage -- the ONE place that says what a stage does with optical flow.
+        takes_flows: its temporal module is a Trajectory_multi_head (`aligned is not None`), the only one that is handed the flows; only
+        then does forward() smooth them.  keeps_flow_scale: VMG.compute_flow runs SPyNet at this stage's scale (VMG.flow_scales) -- every
+        stage that takes flows, and also a window-attention stage (`aligned is None`, temporal_empty = False): it reads no flows, but no
+        shipped config has one, and a config with temporal_empty = False is specified to compute the flows of every scale as it always
+        did.  In the shipped configs (temporal_empty) the two are the same."""
+        takes = aligned is not None
+        return takes, takes or not empty_aligned
 
     @staticmethod
     def flow_smoothing(flow, r):
@@ -577,7 +611,7 @@ class Mlp_encoder(nn.Module):
     def forward(self, x, flow_forward=None, flow_backward=None):
         B, T, H, W, C = x.shape
         shortcut = x
-        if flow_forward is not None and self.if_smooth:
+        if flow_forward is not None and self.if_smooth and (self.takes_flows or self._smooth_unused):  # (smoothed only to be passed on)
             flow_backward = self.flow_smoothing(flow_backward, self.region_range)
             flow_forward = self.flow_smoothing(flow_forward, self.region_range)
         for blk in self.mlp_blocks:
@@ -698,6 +732,12 @@ class VMG(nn.Module):
             self.sc_64_16 = nn.Sequential(nn.Conv2d(embed_dim[0], embed_dim[2], 1, 1, 0), nn.GroupNorm(1, embed_dim[2]), nn.ReLU())
             self.sc_32_8 = nn.Sequential(nn.Conv2d(embed_dim[1], embed_dim[3], 1, 1, 0), nn.GroupNorm(1, embed_dim[3]), nn.ReLU())
         self.mlp_wd_param = [p for name, p in self.named_parameters() if ".mlp_blocks." in name]
+        # encoder scales at which compute_flow runs SPyNet: those where encoder_layers[i] or the decoder stage of the same scale keeps its
+        # flow scale (Mlp_encoder.flow_use) -- scale 0 alone in every shipped config; the other scales get None
+        nd = self.num_dec_layers
+        stages = [[self.encoder_layers[i]] + ([self.decoder_layers[nd - 1 - i]] if 0 <= nd - 1 - i < nd else []) for i in range(self.num_enc_layers)]
+        self.flow_scales = frozenset(i for i, st in enumerate(stages) if any(m.keeps_flow_scale for m in st))
+        self._flows_all_scales = False  # tests only: the flows of every scale, as before the consumer set existed
         self._forward_calls = 0  # (a plain attribute, not a buffer: the state-dict keys are the reference's)
         self.apply(self._init_weights)
 
@@ -756,11 +796,21 @@ class VMG(nn.Module):
             if torch.linalg.norm(a - b.flip(1)) == 0:
                 self.frames_mirror = True
 
+    def _set_flows_all_scales(self, on: bool) -> None:
+        """Tests only: SPyNet and the smoothing at every scale, read or not, as before flow_scales existed."""
+        self._flows_all_scales = bool(on)
+        for m in list(self.encoder_layers) + list(self.decoder_layers):
+            m._smooth_unused = bool(on)
+
     def compute_flow(self, lrs):
-        """Per encoder scale: SPyNet forward/backward flows (models/vmg.py:435-464)."""
+        """Per encoder scale: SPyNet forward/backward flows (models/vmg.py:435-464); None for a scale no stage takes flows at (flow_scales)."""
         B, T, C, H, W = lrs.shape
         fwd, bwd = [], []
         for i in range(self.num_enc_layers):
+            if i not in self.flow_scales and not self._flows_all_scales:  # no stage reads this scale's flows
+                fwd.append(None)
+                bwd.append(None)
+                continue
             h, w = H // (2 ** i), W // (2 ** i)
             xi = F.adaptive_avg_pool2d(lrs.reshape(B * T, C, H, W), (h, w)).reshape(B, T, C, h, w)
             a = xi[:, :-1].reshape(-1, C, h, w)
