@@ -294,7 +294,9 @@ int vmg_conv_wgrad_plan(int entry, int dtype, int ks, int nprob, int npairs, int
  * vmg_pair_steps     the same pairing through a POINTER LIST of the t step tensors (2n frames each; the recurrence's step outputs / step
  *                    gradients are separate allocations): mode 0 steps -> a = backward-sweep features, b = forward-sweep features, both (n, t)
  *                    in frame order (trajectory.py:394-395, 479: `feats_.insert(0, ...)` / `append` + stack); mode 1 the inverse (its
- *                    backward); mode 2 a[i, f] = steps[t-1-f][i] + steps[f][n+i] (the gradient of the pairing, fp32 sum, one rounding).  t <= 64.
+ *                    backward); mode 2 a[i, f] = steps[t-1-f][i] + steps[f][n+i] (the gradient of the pairing, fp32 sum, one rounding).  Any t: up
+ *                    to 64 steps travel in the arguments of ONE launch; longer clips take one launch per range of 64 steps (mode 2: of 32
+ *                    destination frames, which read 64 steps) -- the same bits, no allocation, no synchronisation.
  * vmg_layernorm_fwd  y = (x - mean) * rstd * w + b over the last dim C of (M, C) rows, eps inside the sqrt; mean / rstd
  *                    (fp32, M each) are written when non-null.  nn.LayerNorm at function.py:1164,1195; layers.py:768-775;
  *                    swin_3d.py:717,741.
@@ -395,6 +397,22 @@ int vmg_ltam_bwd(int dtype, const void* q, const void* const* keys, const void* 
                  const float* decay, const void* out, const float* lse, const void* dout, void* dq, void* const* dk_acc,
                  void* const* dv_acc, float* drpe, int n, int h, int w, int c, int heads, int wh, int ww, int t, float scale,
                  void* stream);
+/* The same two operations over ANY number of key-frames (t >= 1).  vmg_ltam_fwd / _bwd carry the key / value / accumulator pointers in their
+ * kernel arguments and refuse a 33rd key-frame; these entries take the same host pointer lists and put them into a device table in `ws`
+ * (ws_bytes >= vmg_ltam_tab_bytes(t) bytes of device memory, 8-byte aligned, caller-owned, contents irrelevant) with a small fill kernel ON THE
+ * STREAM, 32 key-frames per launch -- no host-to-device copy, so the call can be captured into a hipGraph and replayed -- and then run the same
+ * kernels, which read key-frame j's pointers from the table: same key-frame loop, same arithmetic, same bits for out / lse / dq.  All calls that share a
+ * workspace must be ordered on one stream, and the workspace must stay allocated while a captured graph that used it can be replayed.
+ * Route rule (vmg_amd.functional.ltam_route): t <= 32 -> the argument entries (every shipped shape: t <= 17), t > 32 -> these.
+ * t < 1, a null workspace and a workspace that is too small are refused before any launch. */
+int64_t vmg_ltam_tab_bytes(int t);
+int vmg_ltam_fwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const float* rpe,
+                     const float* decay, void* out, float* lse, int n, int h, int w, int c, int heads, int wh, int ww, int t, float scale,
+                     void* ws, int64_t ws_bytes, void* stream);
+int vmg_ltam_bwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const float* rpe,
+                     const float* decay, const void* out, const float* lse, const void* dout, void* dq, void* const* dk_acc,
+                     void* const* dv_acc, float* drpe, int n, int h, int w, int c, int heads, int wh, int ww, int t, float scale,
+                     void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Live kernel timing (bench.py roofline object): HIP events are recorded on the launch stream around every

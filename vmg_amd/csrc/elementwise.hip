@@ -611,6 +611,46 @@ __global__ __launch_bounds__(256) void pair_steps_kernel(const PairStepsK k) {
   Vec* dst = k.mode == 0 ? ot : st;
   for (long long v = v0 + threadIdx.x; v < v1; v += 256) dst[v] = src[v];
 }
+
+// More than PS_MAX_T steps: the same moves, one launch per RANGE whose step pointers fit the kernel arguments.
+//   modes 0, 1: steps [j0, j0 + cnt), cnt <= PS_MAX_T: step[s] = steps[j0 + s]; a step moves independently of the others.
+//   mode 2:     destination frames [j0, j0 + cnt), cnt <= PS_MAX_T / 2, need steps fr and t-1-fr: step[s] = steps[j0 + s] (the forward sweep's
+//               rows) and step[PS_MAX_T / 2 + s] = steps[t - 1 - (j0 + s)] (the backward sweep's).  The sum is pair_steps_kernel's: fp32, one rounding.
+struct PairStepsRangeK {
+  void* step[PS_MAX_T];
+  void* a;
+  void* b;
+  int n, t, chunks, mode, j0, cnt;
+  long long fv;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void pair_steps_range_kernel(const PairStepsRangeK k) {
+  constexpr int VN = 16 / (int)sizeof(T);
+  typedef VecN<T, VN> Vec;
+  const int f = blockIdx.x / k.chunks, ck = blockIdx.x - f * k.chunks;
+  const long long v0 = k.fv * ck / k.chunks, v1 = k.fv * (ck + 1) / k.chunks;
+  if (k.mode == 2) {
+    const int i = f / k.cnt, s = f - i * k.cnt;  // clip i, destination frame j0 + s
+    const Vec* s0 = reinterpret_cast<const Vec*>(k.step[PS_MAX_T / 2 + s]) + (long long)i * k.fv;
+    const Vec* s1 = reinterpret_cast<const Vec*>(k.step[s]) + (long long)(k.n + i) * k.fv;
+    Vec* d = reinterpret_cast<Vec*>(k.a) + ((long long)i * k.t + k.j0 + s) * k.fv;
+    for (long long v = v0 + threadIdx.x; v < v1; v += 256) {
+      const Vec x = s0[v], y = s1[v];
+      Vec o;
+#pragma unroll
+      for (int e = 0; e < VN; ++e) o.v[e] = from_f32<T>(to_f32(x.v[e]) + to_f32(y.v[e]));
+      d[v] = o;
+    }
+    return;
+  }
+  const int s = f / (2 * k.n), r = f - s * 2 * k.n, j = k.j0 + s;  // step j, row r
+  Vec* st = reinterpret_cast<Vec*>(k.step[s]) + (long long)r * k.fv;
+  Vec* ot = r < k.n ? reinterpret_cast<Vec*>(k.a) + ((long long)r * k.t + (k.t - 1 - j)) * k.fv
+                    : reinterpret_cast<Vec*>(k.b) + ((long long)(r - k.n) * k.t + j) * k.fv;
+  const Vec* src = k.mode == 0 ? st : ot;
+  Vec* dst = k.mode == 0 ? ot : st;
+  for (long long v = v0 + threadIdx.x; v < v1; v += 256) dst[v] = src[v];
+}
 }  // namespace
 
 extern "C" int vmg_act_bwd(int dtype, const void* dy, const void* ref, void* out, int64_t n, int act, float slope, float alpha,
@@ -683,14 +723,36 @@ extern "C" int vmg_cast_clear(int dtype, float* acc, const void* add, void* out,
 
 extern "C" int vmg_pair_steps(int dtype, int mode, void* const* steps, void* a, void* b, int n, int t, int64_t frame_elems, void* stream) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "pair_steps: bad dtype");
-  VMG_CHECK(steps && a && (b || mode == 2) && n > 0 && t > 0 && t <= PS_MAX_T && frame_elems > 0 && mode >= 0 && mode <= 2, "pair_steps: bad arguments (t <= %d)", PS_MAX_T);
+  VMG_CHECK(steps && a && (b || mode == 2) && n > 0 && t > 0 && frame_elems > 0 && mode >= 0 && mode <= 2, "pair_steps: bad arguments");
   const int vn = dtype == VMG_BF16 ? 8 : 4;
   VMG_CHECK(frame_elems % vn == 0 && ((uintptr_t)a | (uintptr_t)b) % 16 == 0, "pair_steps: frames must be whole 16-byte vectors, tensors 16-byte aligned");
-  PairStepsK k;
-  for (int j = 0; j < t; ++j) {
-    VMG_CHECK(steps[j] && (uintptr_t)steps[j] % 16 == 0, "pair_steps: step %d: null or unaligned", j);
-    k.step[j] = steps[j];
+  for (int j = 0; j < t; ++j) VMG_CHECK(steps[j] && (uintptr_t)steps[j] % 16 == 0, "pair_steps: step %d: null or unaligned", j);
+  if (t > PS_MAX_T) {  // several launches over step ranges (every check is done: a refusal launches nothing)
+    PairStepsRangeK r;
+    r.a = a; r.b = b; r.n = n; r.t = t; r.mode = mode;
+    r.fv = frame_elems / vn;
+    const int per = mode == 2 ? PS_MAX_T / 2 : PS_MAX_T;
+    for (int j0 = 0; j0 < t; j0 += per) {
+      r.j0 = j0; r.cnt = t - j0 < per ? t - j0 : per;
+      for (int s = 0; s < PS_MAX_T; ++s) r.step[s] = nullptr;
+      for (int s = 0; s < r.cnt; ++s) {
+        r.step[s] = steps[j0 + s];
+        if (mode == 2) r.step[PS_MAX_T / 2 + s] = steps[t - 1 - (j0 + s)];
+      }
+      const long long frames = mode == 2 ? (long long)n * r.cnt : 2LL * n * r.cnt;
+      long long chunks = cdiv64(2048, frames);  // ~2 048 blocks per launch
+      if (chunks > cdiv64(r.fv, 256)) chunks = cdiv64(r.fv, 256);
+      if (chunks < 1) chunks = 1;
+      r.chunks = (int)chunks;
+      const dim3 grid((unsigned)(frames * chunks));
+      if (dtype == VMG_BF16) hipLaunchKernelGGL(pair_steps_range_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, r);
+      else hipLaunchKernelGGL(pair_steps_range_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, r);
+      VMG_LAUNCH_CHECK();
+    }
+    return 0;
   }
+  PairStepsK k;
+  for (int j = 0; j < t; ++j) k.step[j] = steps[j];
   k.a = a; k.b = b; k.n = n; k.t = t; k.mode = mode;
   k.fv = frame_elems / vn;
   const long long frames = mode == 2 ? (long long)n * t : 2LL * n * t;

@@ -13,13 +13,16 @@
 // Thread mapping: 256 threads = 64 tile pixels x 4 heads (thread = pixel * 4 + head); a thread owns the D = C/4
 // channel slice of its head for its pixel, as a query (forward, dq) and as a key/value position (dK, dV).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
 constexpr int LT_TILE = 8;        // tile edge in pixels
 constexpr int LT_PIX = 64;        // pixels per tile
 constexpr int LT_HEADS = 4;       // heads (all shipped configs: traj_heads = 4)
-constexpr int LT_MAX_T = 32;      // key-frames per call (cfg4: ceil(50/3) = 17)
+constexpr int LT_MAX_T = 32;      // key-frames per call of the argument route (cfg4: ceil(50/3) = 17); the table route has no limit
+constexpr int LT_FILL_T = 32;     // key-frames whose pointers one launch of the table's fill kernel carries in its arguments
+constexpr int LT_TAB_SETS = 4;    // pointer sets of the table: keys, values, dK accumulators, dV accumulators, t pointers each
 
 struct LtamK {
   const char* q;
@@ -41,6 +44,28 @@ struct LtamK {
   int tiles_x, tiles_y;
   int dbg;  // diagnostics build only (env VMG_LTAM_DBG): 1 no scatter of dK / dV, 2 no key side, 4 no query side, 8 no gathers after the first key-frame
 };
+// Table route: the same arguments + the device table; k / v / dk_acc / dv_acc above stay empty.
+struct LtamTabK : LtamK {
+  void* const* tab;  // [LT_TAB_SETS][t] device pointers in the caller's workspace
+};
+
+// Where key-frame j's tensors are found.  LtamK: in the kernel arguments (at most LT_MAX_T key-frames).  LtamTabK: in the device table a.tab, which
+// ltam_fill_kernel wrote on the same stream before this launch -- any number of key-frames.  Nothing else differs between the routes: the kernels
+// below take the argument struct as a template parameter and branch on it (if constexpr) where they read key-frame j's four pointers.
+template <typename A>
+constexpr bool lt_is_tab = std::is_same<A, LtamTabK>::value;
+
+// The table is written ON THE STREAM (no host-to-device copy: the call stays capturable into a hipGraph), LT_FILL_T key-frames per launch: thread
+// (set, i) stores pointer i of its set, an ordinary 8-byte vector store.
+struct LtamFillK {
+  void* p[LT_TAB_SETS][LT_FILL_T];
+  void** tab;
+  int t, j0, cnt, sets;  // table stride, first key-frame of this launch, key-frames in it (<= LT_FILL_T), sets in use (2 forward, 4 backward)
+};
+__global__ __launch_bounds__(LT_TAB_SETS * LT_FILL_T) void ltam_fill_kernel(const LtamFillK f) {
+  const int s = threadIdx.x / LT_FILL_T, i = threadIdx.x - s * LT_FILL_T;
+  if (s < f.sets && i < f.cnt) f.tab[(long long)s * f.t + f.j0 + i] = f.p[s][i];
+}
 
 __device__ __forceinline__ int nearest_index(float lx, float ly, int w, int h) {
   // grid = 2*l/max(size-1,1) - 1; ATen unnormalise ((g+1)/2)*(size-1); nearbyint; zeros padding -> -1
@@ -114,8 +139,8 @@ __device__ __forceinline__ void load_slice(const T* p, float (&o)[D]) {
   }
 }
 
-template <typename T, int D>
-__global__ __launch_bounds__(256) void ltam_fwd_kernel(const LtamK a) {
+template <typename T, int D, typename A>
+__global__ __launch_bounds__(256) void ltam_fwd_kernel(const A a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int c = LT_HEADS * D, RS = c + 16 / sizeof(T);  // channels (== a.c: the dispatch picks D from it), padded row stride (elements)
   T* qt = reinterpret_cast<T*>(smem);
@@ -173,8 +198,13 @@ __global__ __launch_bounds__(256) void ltam_fwd_kernel(const LtamK a) {
       sidx[tid] = s;
     }
     __syncthreads();
-    rk.fetch(reinterpret_cast<const T*>(a.k[j]) + img * c, sidx, tid);
-    rv.fetch(reinterpret_cast<const T*>(a.v[j]) + img * c, sidx, tid);
+    if constexpr (lt_is_tab<A>) {
+      rk.fetch(reinterpret_cast<const T*>(a.tab[j]) + img * c, sidx, tid);
+      rv.fetch(reinterpret_cast<const T*>(a.tab[a.t + j]) + img * c, sidx, tid);
+    } else {
+      rk.fetch(reinterpret_cast<const T*>(a.k[j]) + img * c, sidx, tid);
+      rv.fetch(reinterpret_cast<const T*>(a.v[j]) + img * c, sidx, tid);
+    }
     rk.store(kt, RS, tid);
     rv.store(vt, RS, tid);
     __syncthreads();
@@ -238,8 +268,8 @@ __device__ __forceinline__ void scatter_rows(void* acc, long long img, const flo
 #else
 #define LT_ABL(bit) false
 #endif
-template <typename T, int D>
-__global__ __launch_bounds__(256) void ltam_bwd_kernel(const LtamK a) {
+template <typename T, int D, typename A>
+__global__ __launch_bounds__(256) void ltam_bwd_kernel(const A a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int c = LT_HEADS * D, RS = c + 16 / sizeof(T);
   T* kt = reinterpret_cast<T*>(smem);
@@ -314,8 +344,13 @@ __global__ __launch_bounds__(256) void ltam_bwd_kernel(const LtamK a) {
     }
     __syncthreads();
     if (!(LT_ABL(8) && j > 0)) {
-      rk.fetch(reinterpret_cast<const T*>(a.k[j]) + img * c, sidx, tid);
-      rv.fetch(reinterpret_cast<const T*>(a.v[j]) + img * c, sidx, tid);
+      if constexpr (lt_is_tab<A>) {
+        rk.fetch(reinterpret_cast<const T*>(a.tab[j]) + img * c, sidx, tid);
+        rv.fetch(reinterpret_cast<const T*>(a.tab[a.t + j]) + img * c, sidx, tid);
+      } else {
+        rk.fetch(reinterpret_cast<const T*>(a.k[j]) + img * c, sidx, tid);
+        rv.fetch(reinterpret_cast<const T*>(a.v[j]) + img * c, sidx, tid);
+      }
     }
     rk.store(kt, RS, tid);
     rv.store(vt, RS, tid);
@@ -403,12 +438,14 @@ __global__ __launch_bounds__(256) void ltam_bwd_kernel(const LtamK a) {
 #pragma unroll
       for (int d = 0; d < D; ++d) rowbuf[p * c + hd * D + d] = (dkn[d] - kn[d] * nd) * inv;
       __syncthreads();
-      scatter_rows<c>(a.dk_acc[j], img, rowbuf, sidx, selfidx, tid, LT_ABL(1));
+      if constexpr (lt_is_tab<A>) scatter_rows<c>(a.tab[2 * a.t + j], img, rowbuf, sidx, selfidx, tid, LT_ABL(1));
+      else scatter_rows<c>(a.dk_acc[j], img, rowbuf, sidx, selfidx, tid, LT_ABL(1));
       __syncthreads();
 #pragma unroll
       for (int d = 0; d < D; ++d) rowbuf[p * c + hd * D + d] = dv[d];
       __syncthreads();
-      scatter_rows<c>(a.dv_acc[j], img, rowbuf, sidx, selfidx, tid, LT_ABL(1));
+      if constexpr (lt_is_tab<A>) scatter_rows<c>(a.tab[3 * a.t + j], img, rowbuf, sidx, selfidx, tid, LT_ABL(1));
+      else scatter_rows<c>(a.dv_acc[j], img, rowbuf, sidx, selfidx, tid, LT_ABL(1));
     }
   }
   // query normalisation Jacobian
@@ -428,13 +465,13 @@ __global__ __launch_bounds__(256) void ltam_bwd_kernel(const LtamK a) {
   for (int i = tid; i < LT_HEADS * wq * wq; i += 256) atomicAdd(&a.drpe[i], drpe_s[i]);
 }
 
-template <typename T, int D>
-int launch_ltam(const LtamK& k, bool backward, hipStream_t st) {
+template <typename T, int D, typename A>
+int launch_ltam(const A& k, bool backward, hipStream_t st) {
   const int RS = k.c + 16 / (int)sizeof(T);
   const int grid = k.n * k.tiles_y * k.tiles_x;
   if (!backward) {
     const int lds = 3 * LT_PIX * RS * (int)sizeof(T) + LT_PIX * 4 + 2 * LT_PIX * 4;
-    auto fn = ltam_fwd_kernel<T, D>;
+    auto fn = ltam_fwd_kernel<T, D, A>;
     static bool set[VMG_MAX_DEVICES] = {};  // the attribute is per device
     const int dev = vmg_current_device();
     if (!set[dev]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set[dev] = true; }
@@ -444,7 +481,7 @@ int launch_ltam(const LtamK& k, bool backward, hipStream_t st) {
     // (bf16, 144 channels, 2 x 2 windows: 81 152 B -- two workgroups per CU)
     const int lds = 4 * LT_PIX * RS * (int)sizeof(T) + (2 * LT_PIX + 2 * LT_PIX * LT_HEADS + LT_HEADS * wq * wq) * 4 + 2 * LT_PIX * 4;
     VMG_CHECK(lds <= 160 * 1024, "ltam_bwd: LDS request %d B exceeds 160 KiB", lds);
-    auto fn = ltam_bwd_kernel<T, D>;
+    auto fn = ltam_bwd_kernel<T, D, A>;
     static bool set[VMG_MAX_DEVICES] = {};  // the attribute is per device
     const int dev = vmg_current_device();
     if (!set[dev]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set[dev] = true; }
@@ -454,24 +491,25 @@ int launch_ltam(const LtamK& k, bool backward, hipStream_t st) {
   return 0;
 }
 
-template <typename T>
-int dispatch_d(const LtamK& k, bool backward, hipStream_t st) {
+template <typename T, typename A>
+int dispatch_d(const A& k, bool backward, hipStream_t st) {
   switch (k.c / LT_HEADS) {
-    case 4: return launch_ltam<T, 4>(k, backward, st);
-    case 8: return launch_ltam<T, 8>(k, backward, st);
-    case 28: return launch_ltam<T, 28>(k, backward, st);
-    case 36: return launch_ltam<T, 36>(k, backward, st);
+    case 4: return launch_ltam<T, 4, A>(k, backward, st);
+    case 8: return launch_ltam<T, 8, A>(k, backward, st);
+    case 28: return launch_ltam<T, 28, A>(k, backward, st);
+    case 36: return launch_ltam<T, 36, A>(k, backward, st);
   }
   vmg_set_error("ltam: head dim %d not instantiated (supported: 4, 8, 28, 36)", k.c / LT_HEADS);
   return -1;
 }
 
 int fill_common(LtamK& k, int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const float* rpe,
-                const float* decay, int n, int h, int w, int c, int heads, int wh, int ww, int t, float scale) {
+                const float* decay, int n, int h, int w, int c, int heads, int wh, int ww, int t, float scale, bool tab = false) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "ltam: bad dtype");
   VMG_CHECK(q && keys && vals && loc && rpe && decay, "ltam: null pointer");
   VMG_CHECK(heads == LT_HEADS, "ltam: heads must be %d", LT_HEADS);
-  VMG_CHECK(t >= 1 && t <= LT_MAX_T, "ltam: 1..%d key-frames", LT_MAX_T);
+  if (tab) VMG_CHECK(t >= 1, "ltam: at least one key-frame");
+  else VMG_CHECK(t >= 1 && t <= LT_MAX_T, "ltam: 1..%d key-frames", LT_MAX_T);
   VMG_CHECK(n > 0 && h > 0 && w > 0 && c % (LT_HEADS * (dtype == VMG_BF16 ? 8 : 4) / LT_HEADS) == 0 && c % LT_HEADS == 0, "ltam: bad shape");
   VMG_CHECK(wh >= 1 && ww >= 1 && LT_TILE % wh == 0 && LT_TILE % ww == 0 && h % wh == 0 && w % ww == 0 && wh * ww <= 16,
             "ltam: window %dx%d must divide 8 and the image", wh, ww);
@@ -479,6 +517,7 @@ int fill_common(LtamK& k, int dtype, const void* q, const void* const* keys, con
   k.q = (const char*)q;
   for (int j = 0; j < t; ++j) {
     VMG_CHECK(keys[j] && vals[j], "ltam: null key/value %d", j);
+    if (tab) continue;  // (the table holds them)
     k.k[j] = (const char*)keys[j];
     k.v[j] = (const char*)vals[j];
   }
@@ -488,7 +527,33 @@ int fill_common(LtamK& k, int dtype, const void* q, const void* const* keys, con
   return 0;
 }
 
+// Table route: the workspace check and the fill launches, ceil(t / LT_FILL_T) of them, ahead of the attention kernel on the same stream.
+int fill_table(LtamTabK& k, const void* const* keys, const void* const* vals, void* const* dk_acc, void* const* dv_acc, int t, void* ws, int64_t ws_bytes,
+               hipStream_t st) {
+  VMG_CHECK(ws && (uintptr_t)ws % 8 == 0, "ltam: table workspace null or not 8-byte aligned");
+  VMG_CHECK(ws_bytes >= (int64_t)LT_TAB_SETS * t * (int64_t)sizeof(void*), "ltam: table workspace of %lld B is too small for %d key-frames (vmg_ltam_tab_bytes)",
+            (long long)ws_bytes, t);
+  LtamFillK f;
+  f.tab = (void**)ws; f.t = t; f.sets = dk_acc ? 4 : 2;
+  for (int j0 = 0; j0 < t; j0 += LT_FILL_T) {
+    f.j0 = j0; f.cnt = t - j0 < LT_FILL_T ? t - j0 : LT_FILL_T;
+    for (int i = 0; i < LT_FILL_T; ++i) {
+      const bool in = i < f.cnt;
+      f.p[0][i] = in ? const_cast<void*>(keys[j0 + i]) : nullptr;
+      f.p[1][i] = in ? const_cast<void*>(vals[j0 + i]) : nullptr;
+      f.p[2][i] = in && dk_acc ? dk_acc[j0 + i] : nullptr;
+      f.p[3][i] = in && dv_acc ? dv_acc[j0 + i] : nullptr;
+    }
+    hipLaunchKernelGGL(ltam_fill_kernel, dim3(1), dim3(LT_TAB_SETS * LT_FILL_T), 0, st, f);
+    VMG_LAUNCH_CHECK();
+  }
+  k.tab = (void* const*)ws;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int64_t vmg_ltam_tab_bytes(int t) { return t < 1 ? 0 : (int64_t)LT_TAB_SETS * t * (int64_t)sizeof(void*); }
 
 extern "C" int vmg_ltam_fwd(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc,
                             const float* rpe, const float* decay, void* out, float* lse, int n, int h, int w, int c, int heads, int wh,
@@ -497,7 +562,7 @@ extern "C" int vmg_ltam_fwd(int dtype, const void* q, const void* const* keys, c
   if (int rc = fill_common(k, dtype, q, keys, vals, loc, rpe, decay, n, h, w, c, heads, wh, ww, t, scale)) return rc;
   VMG_CHECK(out, "ltam_fwd: null output");
   k.out = (char*)out; k.lse = lse;
-  return dtype == VMG_BF16 ? dispatch_d<bf16>(k, false, (hipStream_t)stream) : dispatch_d<float>(k, false, (hipStream_t)stream);
+  return dtype == VMG_BF16 ? dispatch_d<bf16, LtamK>(k, false, (hipStream_t)stream) : dispatch_d<float, LtamK>(k, false, (hipStream_t)stream);
 }
 
 extern "C" int vmg_ltam_bwd(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc,
@@ -516,5 +581,39 @@ extern "C" int vmg_ltam_bwd(int dtype, const void* q, const void* const* keys, c
     k.dk_acc[j] = dk_acc[j];
     k.dv_acc[j] = dv_acc[j];
   }
-  return dtype == VMG_BF16 ? dispatch_d<bf16>(k, true, (hipStream_t)stream) : dispatch_d<float>(k, true, (hipStream_t)stream);
+  return dtype == VMG_BF16 ? dispatch_d<bf16, LtamK>(k, true, (hipStream_t)stream) : dispatch_d<float, LtamK>(k, true, (hipStream_t)stream);
+}
+
+extern "C" int vmg_ltam_fwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc,
+                                const float* rpe, const float* decay, void* out, float* lse, int n, int h, int w, int c, int heads, int wh,
+                                int ww, int t, float scale, void* ws, int64_t ws_bytes, void* stream) {
+  LtamTabK k;
+  if (int rc = fill_common(k, dtype, q, keys, vals, loc, rpe, decay, n, h, w, c, heads, wh, ww, t, scale, true)) return rc;
+  VMG_CHECK(out, "ltam_fwd_tab: null output");
+  VMG_CHECK(c / LT_HEADS == 4 || c / LT_HEADS == 8 || c / LT_HEADS == 28 || c / LT_HEADS == 36, "ltam: head dim %d not instantiated (supported: 4, 8, 28, 36)", c / LT_HEADS);
+  k.out = (char*)out; k.lse = lse;
+  if (int rc = fill_table(k, keys, vals, nullptr, nullptr, t, ws, ws_bytes, (hipStream_t)stream)) return rc;
+  return dtype == VMG_BF16 ? dispatch_d<bf16, LtamTabK>(k, false, (hipStream_t)stream) : dispatch_d<float, LtamTabK>(k, false, (hipStream_t)stream);
+}
+
+extern "C" int vmg_ltam_bwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc,
+                                const float* rpe, const float* decay, const void* out, const float* lse, const void* dout, void* dq,
+                                void* const* dk_acc, void* const* dv_acc, float* drpe, int n, int h, int w, int c, int heads, int wh,
+                                int ww, int t, float scale, void* ws, int64_t ws_bytes, void* stream) {
+  LtamTabK k;
+  if (int rc = fill_common(k, dtype, q, keys, vals, loc, rpe, decay, n, h, w, c, heads, wh, ww, t, scale, true)) return rc;
+  VMG_CHECK(out && lse && dout && dq && dk_acc && dv_acc && drpe, "ltam_bwd_tab: null pointer");
+  VMG_CHECK(c / LT_HEADS == 4 || c / LT_HEADS == 8 || c / LT_HEADS == 28 || c / LT_HEADS == 36, "ltam: head dim %d not instantiated (supported: 4, 8, 28, 36)", c / LT_HEADS);
+  {
+    const int wq = wh * ww, RS = c + 16 / (dtype == VMG_BF16 ? 2 : 4);
+    const long long lds = 4LL * LT_PIX * RS * (dtype == VMG_BF16 ? 2 : 4) + (2 * LT_PIX + 2 * LT_PIX * LT_HEADS + LT_HEADS * wq * wq) * 4 + 2 * LT_PIX * 4;
+    VMG_CHECK(lds <= 160 * 1024, "ltam_bwd: LDS request %lld B exceeds 160 KiB", lds);  // (before the fill launches: a refusal launches nothing)
+  }
+#ifdef VMG_DIAG
+  { const char* e = getenv("VMG_LTAM_DBG"); k.dbg = e ? atoi(e) : 0; }
+#endif
+  k.out = (char*)out; k.lse = (float*)lse; k.dout = (const char*)dout; k.dq = (char*)dq; k.drpe = drpe;
+  for (int j = 0; j < t; ++j) VMG_CHECK(dk_acc[j] && dv_acc[j], "ltam_bwd: null accumulator %d", j);
+  if (int rc = fill_table(k, keys, vals, dk_acc, dv_acc, t, ws, ws_bytes, (hipStream_t)stream)) return rc;
+  return dtype == VMG_BF16 ? dispatch_d<bf16, LtamTabK>(k, true, (hipStream_t)stream) : dispatch_d<float, LtamTabK>(k, true, (hipStream_t)stream);
 }

@@ -1565,6 +1565,15 @@ def grad_bank(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+LTAM_ARG_KEYFRAMES = 32  # key-frames whose pointers fit the attention kernels' arguments (csrc/ltam.hip LT_MAX_T)
+
+
+def ltam_route(t: int) -> str:
+    """Which pair of entry points serves a trajectory-attention call over t key-frames.  'args': vmg_ltam_fwd / _bwd, the pointers travel in the kernel
+    arguments (every shipped shape: t <= 17).  'table': vmg_ltam_fwd_tab / _bwd_tab, the kernels read them from a device table filled on the stream."""
+    return "args" if t <= LTAM_ARG_KEYFRAMES else "table"
+
+
 class _LTAM(_Fn):
     @staticmethod
     def forward(ctx, q, loc, rpe, decay_v, cfg, *kv):
@@ -1575,7 +1584,8 @@ class _LTAM(_Fn):
         q = q.contiguous()
         loc = loc.contiguous()
         rpe_c = rpe.detach().contiguous()
-        out, lse = K.ltam_forward(q, keys, vals, loc, rpe_c, decay_v, heads, wh, ww, scale)
+        fwd = K.ltam_forward if ltam_route(t) == "args" else K.ltam_forward_tab
+        out, lse = fwd(q, keys, vals, loc, rpe_c, decay_v, heads, wh, ww, scale)
         ctx.cfg = cfg
         ctx.t = t
         # the table's gradient: in the deferred weight-gradient mode every call of the pass adds straight into .grad (no zero-filled temporary per call, no
@@ -1601,8 +1611,9 @@ class _LTAM(_Fn):
             if b.buf is None:
                 b.buf = K.ACC_POOL.take(q.shape, q.device) if q.dtype != torch.float32 else torch.zeros_like(q, dtype=torch.float32)
             into.append(b.buf)
-        dq, dk, dv, drpe = K.ltam_backward(q, keys, vals, loc, rpe, decay_v, out, lse, dout, heads, wh, ww, scale, dk_into=into[:t], dv_into=into[t:],
-                                           drpe_into=DEFERRED.grad_of(ctx.rpe_param) if ctx.direct else None)
+        bwd = K.ltam_backward if ltam_route(t) == "args" else K.ltam_backward_tab
+        dq, dk, dv, drpe = bwd(q, keys, vals, loc, rpe, decay_v, out, lse, dout, heads, wh, ww, scale, dk_into=into[:t], dv_into=into[t:],
+                               drpe_into=DEFERRED.grad_of(ctx.rpe_param) if ctx.direct else None)
         if ctx.direct:
             DEFERRED.written(ctx.gen, ctx.rpe_param)
             drpe = None

@@ -921,9 +921,13 @@ def conv_wgrad3_multi_ok(x: torch.Tensor, dy: torch.Tensor, ks: int) -> bool:
     return all(ps % 8 == 0 and ps >= (c + 7) // 8 * 8 for ps, c in strides)
 
 
+WGRAD_MULTI_PAIRS = 16  # (x, dy) pairs per problem that one launch of the multi entries sums (csrc/conv_wgrad.hip WG_MAX_PAIRS)
+
+
 def _wgrad_multi(name: str, probs, dims: Sequence[int]):
     """The body of conv_wgrad3_multi (dims = N, H, W) and linear_wgrad2_multi (dims = M,): checks that the problems share one shape, then
-    launches vmg_<name> on them, eight per launch."""
+    launches vmg_<name> on them, eight problems and WGRAD_MULTI_PAIRS pairs per launch: the gradients are added to, so a longer list of pairs (a
+    weight of the recurrence has one pair per frame of the clip) is summed over several launches."""
     conv3 = len(dims) == 3
     M = dims[0] * dims[1] * dims[2] if conv3 else dims[0]
     xs0, dys0, dW0 = probs[0][:3]
@@ -937,13 +941,15 @@ def _wgrad_multi(name: str, probs, dims: Sequence[int]):
     for s in range(0, len(probs), 8):
         grp = probs[s:s + 8]
         n = len(grp)
-        xa = (ctypes.c_void_p * (n * npairs))(*[t.data_ptr() for g in grp for t in g[0]])
-        da = (ctypes.c_void_p * (n * npairs))(*[t.data_ptr() for g in grp for t in g[1]])
         wa = (ctypes.c_void_p * n)(*[g[2].data_ptr() for g in grp])
         ba = (ctypes.c_void_p * n)(*[(g[3].data_ptr() if g[3] is not None else None) for g in grp])
         sa = (ctypes.c_float * n)(*[float(g[4]) for g in grp])
-        hip.check(entry(n, npairs, xa, da, *dims, xps, Cin, dps, Cout, wa, I_total, 0, 0, ba, sa, ws.data_ptr(), ws.numel(), hip.stream_ptr()),
-                  "vmg_" + name)
+        for p0 in range(0, npairs, WGRAD_MULTI_PAIRS):
+            p1 = min(npairs, p0 + WGRAD_MULTI_PAIRS)
+            xa = (ctypes.c_void_p * (n * (p1 - p0)))(*[t.data_ptr() for g in grp for t in g[0][p0:p1]])
+            da = (ctypes.c_void_p * (n * (p1 - p0)))(*[t.data_ptr() for g in grp for t in g[1][p0:p1]])
+            hip.check(entry(n, p1 - p0, xa, da, *dims, xps, Cin, dps, Cout, wa, I_total, 0, 0, ba, sa, ws.data_ptr(), ws.numel(), hip.stream_ptr()),
+                      "vmg_" + name)
 
 
 def linear_wgrad2_multi(probs, M: int):
@@ -1032,7 +1038,35 @@ def _ltam_check_tables(rpe, decay, heads, wh, ww):
         raise HipError(f"ltam: decay must hold {heads} contiguous values, got {tuple(decay.shape)}")
 
 
-def ltam_forward(q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
+class LtamTables:
+    """The device workspace of the table route (vmg_ltam_fwd_tab / _bwd_tab), one per device and stream: the calls that share a workspace must be
+    ordered on one stream (a call's fill kernel overwrites the table the previous call's kernel read).  It grows when t grows.  A superseded buffer
+    is retired, not freed: a captured hipGraph has the table's ADDRESS baked into its fill and attention nodes (as PackPlan's entry tables)."""
+
+    def __init__(self):
+        self.bufs = {}
+        self.retired = []
+
+    def get(self, t: int, device) -> torch.Tensor:
+        need = hip.lib().vmg_ltam_tab_bytes(t)
+        key = (device.index if device.index is not None else torch.cuda.current_device(), hip.stream_ptr())
+        buf = self.bufs.get(key)
+        if buf is None or buf.numel() < need:
+            if buf is not None:
+                self.retired.append(buf)
+            buf = self.bufs[key] = torch.empty(max(need, 4096), dtype=torch.uint8, device=device)
+        return buf
+
+    def clear(self):
+        """The caller's explicit decision: no captured graph that used the table route will be replayed again."""
+        self.bufs.clear()
+        self.retired.clear()
+
+
+LTAM_TABLES = LtamTables()
+
+
+def _ltam_forward(tab, q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
     hip.require_cuda(q, loc, rpe, decay, *keys, *vals)
     n, h, w, c = q.shape
     t = len(keys)
@@ -1044,13 +1078,41 @@ def ltam_forward(q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
     _ltam_check_tables(rpe, decay, heads, wh, ww)
     out = torch.empty_like(q)
     lse = torch.empty((n, h, w, heads), dtype=torch.float32, device=q.device)
+    if tab:
+        if t < 1:
+            raise HipError("ltam_forward_tab: at least one key-frame")
+        ws = LTAM_TABLES.get(t, q.device)
+        hip.check(hip.lib().vmg_ltam_fwd_tab(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), rpe.data_ptr(),
+                                             decay.data_ptr(), out.data_ptr(), lse.data_ptr(), n, h, w, c, heads, wh, ww, t, scale,
+                                             ws.data_ptr(), ws.numel(), hip.stream_ptr()), "vmg_ltam_fwd_tab")
+        return out, lse
     hip.check(hip.lib().vmg_ltam_fwd(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), rpe.data_ptr(),
                                      decay.data_ptr(), out.data_ptr(), lse.data_ptr(), n, h, w, c, heads, wh, ww, t, scale,
                                      hip.stream_ptr()), "vmg_ltam_fwd")
     return out, lse
 
 
+def ltam_forward(q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
+    """Key-frame pointers in the kernel arguments: at most 32 key-frames (vmg_ltam_fwd)."""
+    return _ltam_forward(False, q, keys, vals, loc, rpe, decay, heads, wh, ww, scale)
+
+
+def ltam_forward_tab(q, keys, vals, loc, rpe, decay, heads, wh, ww, scale):
+    """ltam_forward over any number of key-frames: their pointers in a device table (vmg_ltam_fwd_tab, workspace LTAM_TABLES).  Same checks, same bits."""
+    return _ltam_forward(True, q, keys, vals, loc, rpe, decay, heads, wh, ww, scale)
+
+
 def ltam_backward(q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww, scale, dk_into=None, dv_into=None, drpe_into=None):
+    """Key-frame pointers in the kernel arguments: at most 32 key-frames (vmg_ltam_bwd).  See _ltam_backward."""
+    return _ltam_backward(False, q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww, scale, dk_into, dv_into, drpe_into)
+
+
+def ltam_backward_tab(q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww, scale, dk_into=None, dv_into=None, drpe_into=None):
+    """ltam_backward over any number of key-frames (vmg_ltam_bwd_tab, workspace LTAM_TABLES): same checks, same dk_into / dv_into / drpe_into semantics."""
+    return _ltam_backward(True, q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww, scale, dk_into, dv_into, drpe_into)
+
+
+def _ltam_backward(tab, q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww, scale, dk_into=None, dv_into=None, drpe_into=None):
     """dq, dk[j], dv[j], drpe.  dk / dv are FP32 sums (q's shape) for every tensor dtype: the caller rounds them once.  dk_into / dv_into: per
     key-frame an existing fp32 accumulator to scatter into (the gradient of a frame that several calls attend to is summed by the kernel's
     atomics, see functional.grad_bank), or None for a fresh zeroed one.  drpe_into: an fp32 tensor of rpe's shape to ADD the table gradient into (the
@@ -1084,6 +1146,15 @@ def ltam_backward(q, keys, vals, loc, rpe, decay, out, lse, dout, heads, wh, ww,
     if drpe_into is not None and (drpe_into.shape != rpe.shape or drpe_into.dtype != torch.float32 or not drpe_into.is_contiguous()):
         raise HipError("ltam_backward: drpe_into must be a contiguous fp32 tensor of the table's shape")
     drpe = drpe_into if drpe_into is not None else torch.zeros_like(rpe)
+    if tab:
+        if t < 1:
+            raise HipError("ltam_backward_tab: at least one key-frame")
+        ws = LTAM_TABLES.get(t, q.device)
+        hip.check(hip.lib().vmg_ltam_bwd_tab(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), rpe.data_ptr(),
+                                             decay.data_ptr(), out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dq.data_ptr(), _ptrs(dk), _ptrs(dv),
+                                             drpe.data_ptr(), n, h, w, c, heads, wh, ww, t, scale, ws.data_ptr(), ws.numel(), hip.stream_ptr()),
+                  "vmg_ltam_bwd_tab")
+        return dq, dk, dv, drpe
     hip.check(hip.lib().vmg_ltam_bwd(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), rpe.data_ptr(),
                                      decay.data_ptr(), out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dq.data_ptr(), _ptrs(dk), _ptrs(dv),
                                      drpe.data_ptr(), n, h, w, c, heads, wh, ww, t, scale, hip.stream_ptr()), "vmg_ltam_bwd")
