@@ -132,10 +132,35 @@ typedef struct vmg_conv_desc {
               *   wave-private LDS (bf16, one dense source of <= 160 channels, cout_tiles 3 or 5, 16-byte aligned output rows);
               * VMG_CONV_WSTAT -- weights-stationary 3x3 (bf16, one source of <= 64 channels, cout_tiles 1, 3 or 4: a persistent
               *   workgroup per CU keeps the packed weights in LDS and walks over 128-pixel tiles; the HR head, models/vmg.py:629-632).
-              * VMG_CONV_LINEAR_WRES and VMG_CONV_WSTAT are hints: a call they do not cover runs on the general kernel */
+              * VMG_CONV_LINEAR_WRES and VMG_CONV_WSTAT are hints: a call they do not cover runs on the general kernel
+              *   (vmg_conv_fwd_plan says which kernel a call runs).  LINEAR_WRES covers: bf16, ks 1, 16-byte epilogue (Cout % 16 == 0, no
+              *   pixel_shuffle, out / out_pre / res / aux 16-byte aligned with pixel strides % 8 == 0), cout_tiles 3 or 5, and either ONE source
+              *   of <= 160 channels whose conflict-free LDS pixel stride is the dense one -- channels % 32 == 16: 16, 48, 80, 112, 144 --
+              *   (linear_wres_kernel<cout_tiles>), or, with cout_tiles 3 only, one source that splits into two equal blocks of <= 160 channels,
+              *   each a multiple of 8 -- 176, 192, .. 320 -- (linear_wres_kernel<3, 2>).  Any other call with this hint -- other channel
+              *   counts, several sources, unaligned rows -- runs conv_igemm_kernel as with VMG_CONV_GENERAL. */
 } vmg_conv_desc;
 
 int vmg_conv_fwd(const vmg_conv_desc* d, void* stream);
+/* The decision behind vmg_conv_fwd, without a launch: which kernel instance a call with this descriptor runs, and with which grid.  It is
+ * the function vmg_conv_fwd itself dispatches through.  No pointer of the descriptor is dereferenced (only null-ness and alignment are read),
+ * and with ncu > 0 (the compute-unit count to plan for) no device call is made; ncu = 0 takes the current device's count.  Writes
+ * VMG_CONV_PLAN_INTS ints to plan:
+ *   [0] kernel family VMG_CONV_FAM_*       [1] dtype   [2] KS   [3] MT (16-pixel rows per wave)   [4] NTB (16-channel tiles per workgroup)
+ *   [5] variant: LINEAR_WRES: NS (source blocks, 1 or 2); WSTAT: NB | FULL << 4 (32-channel blocks; the epilogue with res / aux / pre / GELU);
+ *       else 0
+ *   [6] vec8: 1 = 16-byte epilogue through LDS, 0 = element-wise epilogue
+ *   [7] grid x   [8] grid y (output-channel blocks)   [9] 16-row tiles per wave (LINEAR_WRES only, else 0)   [10] dynamic LDS bytes
+ * Returns -1, with vmg_conv_fwd's message, for a descriptor that vmg_conv_fwd refuses. */
+enum { /* (an enum: the VMG_CONV_ macros are the routes of vmg_conv_desc::deep and nothing else) */
+  VMG_CONV_FAM_IGEMM = 1,       /* conv_igemm_kernel<T, KS, MT, NTB> */
+  VMG_CONV_FAM_KSPLIT = 2,      /* conv_ksplit_kernel<bf16, KS, NTB> */
+  VMG_CONV_FAM_WS = 3,          /* conv_ws_kernel<NTB> */
+  VMG_CONV_FAM_LINEAR_WRES = 4, /* linear_wres_kernel<NTB, NS> */
+  VMG_CONV_FAM_WSTAT = 5,       /* conv_wstat_kernel<NTB, NB, FULL> */
+  VMG_CONV_PLAN_INTS = 11
+};
+int vmg_conv_fwd_plan(const vmg_conv_desc* d, int ncu, int* plan);
 /* ------------------------------------------------------------------------------------------------
  * vmg_resblock_chain_fwd / _bwd -- ResidualBlocksWithInputConv (reference: models/trajectory.py:16-52, 165-221), the 1 + 2*nblk
  * convolutions of one recurrence step, enqueued by ONE call (no host work between the launches):

@@ -11,7 +11,10 @@ two; as long as that integer stays below 2^24 (assert_exact) every partial sum i
 number: the only rounding left is the final one to bf16, and the result must equal round_bf16(fp64 reference) bit for bit.
 
 The data gradient has a spelling of its own (a scatter per tap, dgrad_ref): the transpose_flip packs are then compared with something that
-is not the forward reference with a flipped weight."""
+is not the forward reference with a flipped weight.
+
+ks = 1 (every nn.Linear and 1x1 conv) has references of its own -- linear_ref, dlinear_ref, pixel_shuffle_ref, gelu_ref, gelu_grad_ref --
+that do not go through conv_ref; assert_exact and real_bound take the tap count (taps = 1), epilogue_ref the output dtype."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -67,6 +70,54 @@ def dgrad_ref(dy, w, i0=0, inn=None):
     return dxp[:, 1:H + 1, 1:W + 1].contiguous()
 
 
+def linear_ref(srcs, w, src_off=None, o0=0, on=None):
+    """ks = 1: one fp64 matmul per source over its K slice of w (O, I).  srcs[s] (..., C_s) channels-last with equal leading shapes; source s
+    meets the weight's input channels [src_off[s], src_off[s] + C_s) (default: one after the other); the result holds outputs [o0, o0 + on)."""
+    assert w.dim() == 2
+    on = w.shape[0] - o0 if on is None else on
+    wt = w.double()[o0:o0 + on].t().contiguous()  # (I, on)
+    lead = tuple(srcs[0].shape[:-1])
+    acc = torch.zeros(lead + (on,), dtype=torch.float64)
+    a = 0
+    for s, x in enumerate(srcs):
+        C = x.shape[-1]
+        off = a if src_off is None else src_off[s]
+        a += C
+        assert tuple(x.shape[:-1]) == lead and off + C <= w.shape[1]
+        acc += (x.double().reshape(-1, C) @ wt[off:off + C]).reshape(lead + (on,))
+    return acc
+
+
+def dlinear_ref(dy, w, i0=0, inn=None):
+    """Data gradient of y = x @ w.T, w (O, I): dx = dy @ w[:, i0:i0+inn], in fp64 (what a transpose_flip pack of w computes)."""
+    assert w.dim() == 2 and dy.shape[-1] == w.shape[0]
+    inn = w.shape[1] - i0 if inn is None else inn
+    return dy.double() @ w.double()[:, i0:i0 + inn]
+
+
+def pixel_shuffle_ref(x):
+    """(N, H, W, C) -> (N, 2H, 2W, C/4) in torch's PixelShuffle(2) order, by index arithmetic: out[n, 2y+i, 2x+j, c] = x[n, y, x, 4c + 2i + j]."""
+    N, H, W, C = x.shape
+    assert C % 4 == 0
+    out = torch.empty(N, 2 * H, 2 * W, C // 4, dtype=x.dtype)
+    for i in range(2):
+        for j in range(2):
+            out[:, i::2, j::2, :] = x[..., (2 * i + j)::4]
+    return out
+
+
+def gelu_ref(v):
+    """GELU, erf form, in fp64: v * Phi(v)."""
+    v = v.double()
+    return 0.5 * v * (1.0 + torch.erf(v / np.sqrt(2.0)))
+
+
+def gelu_grad_ref(v):
+    """d/dv gelu(v) = Phi(v) + v * phi(v), in fp64."""
+    v = v.double()
+    return 0.5 * (1.0 + torch.erf(v / np.sqrt(2.0))) + v * torch.exp(-0.5 * v * v) / np.sqrt(2.0 * np.pi)
+
+
 def _is_pow2(v):
     m, _ = np.frexp(abs(float(v)))
     return v != 0 and m == 0.5
@@ -96,15 +147,19 @@ def mask_ref(aux, actgrad, slope):
     return torch.where(aux.double() > 0, torch.ones((), dtype=torch.float64), torch.full((), lo, dtype=torch.float64))
 
 
-def epilogue_ref(acc, bias=None, act=ACT_NONE, slope=0.0, alpha=1.0, aux=None, actgrad=0, res=None, exact=True):
+def epilogue_ref(acc, bias=None, act=ACT_NONE, slope=0.0, alpha=1.0, aux=None, actgrad=0, res=None, exact=True, out_dtype=torch.bfloat16):
     """The epilogue in the kernels' order on the fp64 sums `acc`.  exact: every intermediate is asserted to be an fp32 number and the result
     is (out, out_pre) as bf16 tensors.  A LeakyReLU slope that is no power of two is the one step that may round: v * float32(slope),
     rounded to fp32 as the kernel's single multiplication does (assert_exact admits it only where the bf16 rounding follows directly).
-    GELU: out is None (only out_pre is exact).  exact=False: no intermediate rounding, (out, out_pre) in fp64."""
+    GELU: out is None (only out_pre is exact).  exact=False: no intermediate rounding, (out, out_pre) in fp64.
+    out_dtype = torch.float32 (the fp32 kernels): the exact results are the fp64 values themselves, asserted to be fp32 numbers and returned as
+    fp32 tensors -- nothing is rounded but a LeakyReLU slope that is no power of two, once, as above."""
+    assert out_dtype in (torch.bfloat16, torch.float32)
+    final = round_bf16 if out_dtype == torch.bfloat16 else (lambda t: _f32(t, True, "the fp32 output").float())
     slope32, alpha32 = float(np.float32(slope)), float(np.float32(alpha))
     v = acc if bias is None else acc + bias.double()
     v = _f32(v, exact, "acc + bias") if exact else v
-    pre = round_bf16(v) if exact else v.clone()
+    pre = final(v) if exact else v.clone()
     if act == ACT_GELU:
         return None, pre
     if act == ACT_RELU:
@@ -123,18 +178,18 @@ def epilogue_ref(acc, bias=None, act=ACT_NONE, slope=0.0, alpha=1.0, aux=None, a
     if res is not None:
         v = v + res.double()
         v = _f32(v, True, "v + res") if exact else v
-    return (round_bf16(v) if exact else v), pre
+    return (final(v) if exact else v), pre
 
 
-def assert_exact(family, ci_total, bias=True, res=False, scales=()):
+def assert_exact(family, ci_total, bias=True, res=False, scales=(), taps=9):
     """The invariant, checked before anything runs on the GPU.  Operands k * 2^-s of the family: a partial sum is an integer of at most
-    P = kmax^2 * 9 * ci_total units of 2^-2s, the bias adds at most kmax * 2^s of those units.  Every scale (LeakyReLU slope, alpha, the
+    P = kmax^2 * taps * ci_total units of 2^-2s (taps = 9 for 3x3, 1 for ks = 1), the bias adds at most kmax * 2^s of those units.  Every scale (LeakyReLU slope, alpha, the
     slope of mask mode 2) is a power of two 2^-a_j, a_j >= 0: scaling keeps the integer and moves the grid to 2^-(2s+a), a = sum a_j, on
     which the residual is at most kmax * 2^(s+a) units.  Their sum below 2^24 bounds the integer of every intermediate value (conservatively
     for the ones on coarser grids), so each fits fp32's 24-bit significand.  ONE scale may be no power of two if nothing follows it -- no
     other scale but 1, no residual: then the product is rounded once to fp32 and directly to bf16, which the reference does too."""
     kmax, s = FAMILIES[family]
-    total = kmax * kmax * 9 * ci_total + (kmax * 2 ** s if bias else 0)
+    total = kmax * kmax * taps * ci_total + (kmax * 2 ** s if bias else 0)
     scales = [float(np.float32(c)) for c in scales if float(c) != 1.0]
     odd = [c for c in scales if not _is_pow2(c)]
     if odd:
@@ -170,12 +225,28 @@ def shifted_copy(x, i, tap):
     return out
 
 
-def real_bound(v, S, ci_total):
-    """Per-element bound of |got - v| for real-valued operands: v the fp64 result from the bf16-rounded operands, S = sum |x||w| + |b| +
-    |res|.  e32 = 2 * (9 * ci_total + 4) * 2^-24 * S is the any-order fp32 summation bound of the 9 * ci_total products, the bias, the two
-    scalings and the residual (n terms: n * u * S, u = 2^-24), doubled because the matrix unit's adder may truncate -- one ulp per
-    addition instead of half.  The bf16 rounding of the computed value adds 2^-8 of it (2^-9 would do for round to nearest; an ulp is
-    allowed): |got - v| <= 2^-8 * (|v| + e32) + e32.  ReLU, LeakyReLU, the masks and alpha <= 1 do not enlarge it: they are 1-Lipschitz or
-    do not depend on computed values."""
-    e32 = 2.0 * (9 * ci_total + 4) * 2.0 ** -24 * S
-    return 2.0 ** -8 * (v.abs() + e32) + e32
+def one_hot_linear(O, I, t):
+    """Permutation probe t of a ks = 1 weight: output channel o has a single 1, at input channel (7 * o + 31 * t) % I -- output channel o is then a
+    copy of that input channel, exact for ANY input.  Returns (w (O, I) fp32, input channel per o)."""
+    o = torch.arange(O)
+    i = (7 * o + 31 * t) % I
+    w = torch.zeros(O, I)
+    w[o, i] = 1.0
+    return w, i
+
+
+def sum_bound(S, ci_total, taps=9):
+    """e32 of real_bound: the any-order fp32 summation bound of taps * ci_total products, the bias, the two scalings and the residual over
+    S = sum |x||w| + |b| + |res| (n terms: n * u * S, u = 2^-24), doubled because the matrix unit's adder may truncate."""
+    return 2.0 * (taps * ci_total + 4) * 2.0 ** -24 * S
+
+
+def real_bound(v, S, ci_total, taps=9, out_dtype=torch.bfloat16):
+    """Per-element bound of |got - v| for real-valued operands: v the fp64 result from the operands as the kernel reads them, S = sum |x||w| +
+    |b| + |res|, e32 = sum_bound(S, ci_total, taps).  The rounding of the computed value to the output type adds u_out of it -- 2^-8 for bf16
+    (2^-9 would do for round to nearest; an ulp is allowed), 2^-23 for fp32: |got - v| <= u_out * (|v| + e32) + e32.  ReLU, LeakyReLU, the
+    masks and alpha <= 1 do not enlarge it: they are 1-Lipschitz or do not depend on computed values.  taps: products per input channel
+    (9 for 3x3, 1 for ks = 1)."""
+    e32 = sum_bound(S, ci_total, taps)
+    u_out = 2.0 ** -8 if out_dtype == torch.bfloat16 else 2.0 ** -23
+    return u_out * (v.abs() + e32) + e32

@@ -230,3 +230,101 @@ def _terms_real(x, w):
     cols = torch.stack([xpad[:, ky:ky + H, kx:kx + W] for ky in range(3) for kx in range(3)], -2)
     wt = w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, Ci)
     return (cols[:, :, :, None] * wt[None, None, None]).reshape(N, H, W, w.shape[0], 9 * Ci).numpy()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# ks = 1: the references of tests/test_linear_kernels_gpu.py
+# ------------------------------------------------------------------------------------------------------------------------------------
+from tests import test_linear_kernels_gpu as GL  # noqa: E402
+
+
+def _r64(*shape, seed=0):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+
+
+def test_linear_ref_equals_fp64_linear():
+    x, w = _r64(2, 3, 5, 24, seed=1), _r64(20, 24, seed=2)
+    assert float((CR.linear_ref([x], w) - F.linear(x, w)).abs().max()) <= 1e-12
+    # sources as channel slices, in another order than the weight's; an output slice
+    a, b, c = x[..., :8], x[..., 8:16], x[..., 16:]
+    got = CR.linear_ref([c, a, b], w, src_off=[16, 0, 8], o0=3, on=11)
+    assert tuple(got.shape) == (2, 3, 5, 11) and float((got - F.linear(x, w)[..., 3:14]).abs().max()) <= 1e-12
+    assert float((CR.linear_ref([a, b, c], w) - F.linear(x, w)).abs().max()) <= 1e-12
+    # a K slice of a wider weight
+    assert float((CR.linear_ref([b], w, src_off=[8]) - F.linear(b, w[:, 8:16])).abs().max()) <= 1e-12
+    assert CR.linear_ref([x.float()], w.float()).dtype == torch.float64
+
+
+def test_dlinear_ref_equals_fp64_autograd():
+    x, w, dy = _r64(7, 24, seed=3).requires_grad_(True), _r64(20, 24, seed=4), _r64(7, 20, seed=5)
+    F.linear(x, w).backward(dy)
+    assert float((CR.dlinear_ref(dy, w) - x.grad).abs().max()) <= 1e-12
+    assert float((CR.dlinear_ref(dy, w, i0=8, inn=8) - x.grad[:, 8:16]).abs().max()) <= 1e-12
+    assert tuple(CR.dlinear_ref(dy, w).shape) == (7, 24)  # not the weight's other side
+
+
+def test_pixel_shuffle_ref_equals_torch():
+    x = torch.arange(2 * 3 * 5 * 12, dtype=torch.float32).reshape(2, 3, 5, 12)
+    want = F.pixel_shuffle(x.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
+    got = CR.pixel_shuffle_ref(x)
+    assert tuple(got.shape) == (2, 6, 10, 3) and torch.equal(got, want)
+
+
+def test_gelu_refs_equal_torch_in_fp64():
+    x = torch.cat([torch.linspace(-12, 12, 4001, dtype=torch.float64), torch.tensor([0.0, -0.0, 2.0 ** -126, 30.0, -30.0], dtype=torch.float64)])
+    xg = x.clone().requires_grad_(True)
+    y = F.gelu(xg)
+    y.sum().backward()
+    # (another spelling of the same fp64 formula: a few ulps of the largest value, ulp(30) = 3.6e-15)
+    assert float((CR.gelu_ref(x) - y.detach()).abs().max()) <= 1e-14
+    assert float((CR.gelu_grad_ref(x) - xg.grad).abs().max()) <= 1e-14
+    assert float(CR.gelu_grad_ref(x).abs().max()) < 1.13 and float(CR.gelu_grad_ref(torch.tensor([2.0 ** 0.5])).item()) > 1.128  # sup |gelu'| = 1.129
+    assert CR.gelu_ref(x.float()).dtype == torch.float64
+    assert GL.gelu_sweep().numel() >= 65536 + 6 + 4096 and not bool(torch.isnan(GL.gelu_sweep()).any())
+
+
+def test_assert_exact_with_one_tap_accepts_every_linear_gpu_case_and_no_more():
+    cases = GL.exact_cases()
+    assert len(cases) > 500
+    for c in cases:
+        CR.assert_exact(*GL.exact_args(c), taps=1)
+        assert c.fam == ("full" if sum(c.src_ch) <= 256 else "small")  # "full" wherever one tap admits it
+    CR.assert_exact("full", 256, bias=True, res=True, taps=1)  # 255^2 * 256 + 255 * 2^7 * 2 = 16 711 680 < 2^24
+    assert 255 ** 2 * 256 + 255 * 2 ** 7 * 2 == 16711680 < 2 ** 24
+    with pytest.raises(AssertionError):
+        CR.assert_exact("full", 264, bias=False, taps=1)
+    with pytest.raises(AssertionError):
+        CR.assert_exact("full", 288, taps=1)
+    with pytest.raises(AssertionError):
+        CR.assert_exact("full", 32)  # (the default is still nine taps)
+    CR.assert_exact("full", 32, taps=1)
+
+
+def test_epilogue_ref_for_fp32_outputs_is_the_fp64_value():
+    acc = torch.tensor([[-1.5, 0.75 + 2.0 ** -20, 3.0]], dtype=torch.float64)
+    out, pre = CR.epilogue_ref(acc, torch.tensor([0.5, 0.0, -1.0]), act=CR.ACT_LRELU, slope=0.25, alpha=0.5, out_dtype=torch.float32)
+    assert out.dtype == torch.float32 and pre.dtype == torch.float32
+    assert torch.equal(pre.double(), torch.tensor([[-1.0, 0.75 + 2.0 ** -20, 2.0]], dtype=torch.float64))
+    assert torch.equal(out.double(), torch.tensor([[-0.125, 0.375 + 2.0 ** -21, 1.0]], dtype=torch.float64))
+    out16, _ = CR.epilogue_ref(acc, torch.tensor([0.5, 0.0, -1.0]), act=CR.ACT_LRELU, slope=0.25, alpha=0.5)
+    assert out16.dtype == torch.bfloat16 and float(out16[0, 1]) == 0.375  # (the bf16 default rounds what fp32 keeps)
+    with pytest.raises(AssertionError):
+        CR.epilogue_ref(torch.tensor([1 + 2.0 ** -30], dtype=torch.float64), out_dtype=torch.float32)  # no fp32 number
+    # a slope that is no power of two rounds once, to fp32
+    out, _ = CR.epilogue_ref(torch.tensor([-3.0], dtype=torch.float64), act=CR.ACT_LRELU, slope=0.1, out_dtype=torch.float32)
+    assert float(out) == float(np.float32(-3.0) * np.float32(0.1))
+
+
+def test_permutation_probes_and_the_one_tap_bound():
+    for t in range(3):
+        w, i = CR.one_hot_linear(144, 288, t)
+        assert torch.equal(w.sum(1), torch.ones(144)) and torch.equal(w.argmax(1), i) and len(set(i.tolist())) == 144  # distinct input channels
+        x = torch.randn(5, 288, generator=torch.Generator().manual_seed(t))
+        assert torch.equal(CR.linear_ref([x], w), x[:, i].double())
+    assert not torch.equal(CR.one_hot_linear(16, 8, 0)[1], CR.one_hot_linear(16, 8, 1)[1])
+    v, S = torch.tensor([2.0], dtype=torch.float64), torch.tensor([3.0], dtype=torch.float64)
+    assert float(CR.sum_bound(S, 144, taps=1)) == 2 * 148 * 2.0 ** -24 * 3 and float(CR.sum_bound(S, 144)) == 2 * (9 * 144 + 4) * 2.0 ** -24 * 3
+    e = float(CR.sum_bound(S, 144, taps=1))
+    assert float(CR.real_bound(v, S, 144, taps=1)) == 2.0 ** -8 * (2 + e) + e
+    assert float(CR.real_bound(v, S, 144, taps=1, out_dtype=torch.float32)) == 2.0 ** -23 * (2 + e) + e
+    assert float(CR.real_bound(v, S, 144)) == 2.0 ** -8 * (2 + float(CR.sum_bound(S, 144))) + float(CR.sum_bound(S, 144))

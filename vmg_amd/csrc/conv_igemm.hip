@@ -1891,11 +1891,29 @@ int choose_pixb(int ch, int es, int cb) {
   return best;
 }
 
+// What vmg_conv_fwd launches, decided by conv_plan() below and by nothing else: the launchers take the template instance, the grid, the LDS
+// size and the tiles per wave from here, and vmg_conv_fwd_plan reports the same fields.
+struct ConvPlan {
+  int family;   // VMG_CONV_FAM_*
+  int dtype, ks, mt, ntb;
+  int variant;  // linear_wres: NS; wstat: NB | FULL << 4; else 0
+  int vec8;
+  int gx, gy;   // grid
+  int tpw;      // linear_wres: 16-row tiles per wave; else 0
+  int lds;      // dynamic LDS bytes
+};
+
+// LDS sizes as run-time functions of the tile counts (each launcher asserts its own against the kernel's template constants)
+constexpr int epi_lds_bytes(int ntb) { return 16 * (ntb * 16 * 4 + 16); }
+constexpr int wres_lds_bytes(int ntb, int ns) { return 4 * (2 * 5 * ns * 1024 + ((epi_lds_bytes(ntb) + 1023) & ~1023)); }
+constexpr int wstat_lds_bytes(int nct, int nb) {
+  return 3 * nb * stage_stride(3, nct, 16) + 2 * (((10 * 18 * 9 + 63) / 64) * 1024) + nct * 16 * 4 + 128 * (nct * 64 + 16);
+}
+constexpr int ws_stage_bytes(int nct) { return 3 * nct * 16 * 64; }
+
 template <typename T, int KS, int MT, int NTB>
-int launch_conv(const ConvK& k, int ncb, hipStream_t st) {
-  constexpr int CB = ElemTraits<T>::CHUNKB;
-  const int lds = k.halo_bytes + 2 * stage_stride(KS, NTB, CB);  // halo tile + the 2-slot weight ring
-  VMG_CHECK(lds <= 160 * 1024, "conv: LDS request %d B exceeds 160 KiB", lds);
+int launch_conv(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  const int lds = p.lds;  // halo tile + the 2-slot weight ring
   auto fn = conv_igemm_kernel<T, KS, MT, NTB>;
   static bool attr_set[VMG_MAX_DEVICES] = {};  // the attribute is per device (one code object per device)
   const int dev = vmg_current_device();
@@ -1903,48 +1921,45 @@ int launch_conv(const ConvK& k, int ncb, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set[dev] = true;
   }
-  long long nblk = (KS > 1) ? (long long)k.N * k.tiles_y * k.tiles_x : cdiv64(k.M, 64 * MT);
-  VMG_CHECK(nblk > 0 && nblk < (1ll << 31), "conv: bad grid %lld", nblk);
   // the dominant kernel class of the path: bf16 3x3, one source of 144 channels, 144 outputs (trajectory chains)
   const bool prof = (KS == 3 && sizeof(T) == 2 && k.nsrc == 1 && k.src_ch[0] == 144 && k.Cout == 144) && vmg_prof_before(VMG_PROF_CONV3X3, k.M, st);
-  hipLaunchKernelGGL(fn, dim3((unsigned)nblk, ncb), dim3(256), lds, st, k);
+  hipLaunchKernelGGL(fn, dim3((unsigned)p.gx, p.gy), dim3(256), lds, st, k);
   if (prof) vmg_prof_after(st);
   VMG_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T, int KS, int MT>
-int dispatch_ntb(const ConvK& k, int ntb, int ncb, hipStream_t st) {
-  switch (ntb) {
-    case 1: return launch_conv<T, KS, MT, 1>(k, ncb, st);
-    case 3: return launch_conv<T, KS, MT, 3>(k, ncb, st);
-    case 4: return launch_conv<T, KS, MT, 4>(k, ncb, st);
-    case 5: return launch_conv<T, KS, MT, 5>(k, ncb, st);
-    case 7: return launch_conv<T, KS, MT, 7>(k, ncb, st);
-    case 8: return launch_conv<T, KS, MT, 8>(k, ncb, st);
-    case 9: return launch_conv<T, KS, MT, 9>(k, ncb, st);
+int dispatch_ntb(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  switch (p.ntb) {
+    case 1: return launch_conv<T, KS, MT, 1>(k, p, st);
+    case 3: return launch_conv<T, KS, MT, 3>(k, p, st);
+    case 4: return launch_conv<T, KS, MT, 4>(k, p, st);
+    case 5: return launch_conv<T, KS, MT, 5>(k, p, st);
+    case 7: return launch_conv<T, KS, MT, 7>(k, p, st);
+    case 8: return launch_conv<T, KS, MT, 8>(k, p, st);
+    case 9: return launch_conv<T, KS, MT, 9>(k, p, st);
   }
-  vmg_set_error("conv: cout_tiles must be 1, 3, 4, 5, 7, 8 or 9 (got %d)", ntb);
+  vmg_set_error("conv: cout_tiles must be 1, 3, 4, 5, 7, 8 or 9 (got %d)", p.ntb);
   return -1;
 }
 
 // 7x7 (SPyNet's convs, models/vmg.py:126-173): the pixel-split kernel with 1, 2 or 4 output-channel tiles per workgroup
 template <typename T>
-int dispatch_ks7(const ConvK& k, int ntb, int ncb, hipStream_t st) {
-  switch (ntb) {
-    case 1: return launch_conv<T, 7, 1, 1>(k, ncb, st);
-    case 2: return launch_conv<T, 7, 1, 2>(k, ncb, st);
-    case 4: return launch_conv<T, 7, 1, 4>(k, ncb, st);
+int dispatch_ks7(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  switch (p.ntb) {
+    case 1: return launch_conv<T, 7, 1, 1>(k, p, st);
+    case 2: return launch_conv<T, 7, 1, 2>(k, p, st);
+    case 4: return launch_conv<T, 7, 1, 4>(k, p, st);
   }
-  vmg_set_error("conv (7x7): cout_tiles must be 1, 2 or 4 (got %d)", ntb);
+  vmg_set_error("conv (7x7): cout_tiles must be 1, 2 or 4 (got %d)", p.ntb);
   return -1;
 }
 
+// (conv_plan has already moved k.halo_bytes behind max(halo, scratch): the zero slot and the bias sit there)
 template <typename T, int KS, int NTB>
-int launch_ksplit(const ConvK& k, int ncb, int halo_total, hipStream_t st) {
-  const int scratch = 12 * NTB * 1024;
-  const int lds = (halo_total > scratch ? halo_total : scratch) + 16 + NTB * 16 * 4;
-  VMG_CHECK(lds <= 160 * 1024, "conv (k-split): LDS request %d B exceeds 160 KiB", lds);
+int launch_ksplit(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  const int lds = p.lds;
   auto fn = conv_ksplit_kernel<T, KS, NTB>;
   static bool attr_set[VMG_MAX_DEVICES] = {};  // the attribute is per device (one code object per device)
   const int dev = vmg_current_device();
@@ -1952,33 +1967,29 @@ int launch_ksplit(const ConvK& k, int ncb, int halo_total, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set[dev] = true;
   }
-  long long nblk = (KS > 1) ? (long long)k.N * k.tiles_y * k.tiles_x : cdiv64(k.M, 64);
-  VMG_CHECK(nblk > 0 && nblk < (1ll << 31), "conv: bad grid %lld", nblk);
-  ConvK kk = k;
-  kk.halo_bytes = lds - 16 - NTB * 16 * 4;  // zero slot and bias sit behind max(halo, scratch)
   const bool prof = (KS == 3 && sizeof(T) == 2 && k.nsrc == 1 && k.src_ch[0] == k.Cout && (k.Cout == 144 || k.Cout == 112)) && vmg_prof_before(VMG_PROF_CONV3X3, k.M, st);
-  hipLaunchKernelGGL(fn, dim3((unsigned)nblk, ncb), dim3(256), lds, st, kk);
+  hipLaunchKernelGGL(fn, dim3((unsigned)p.gx, p.gy), dim3(256), lds, st, k);
   if (prof) vmg_prof_after(st);
   VMG_LAUNCH_CHECK();
   return 0;
 }
 
 template <typename T, int KS>
-int dispatch_ksplit(const ConvK& k, int ntb, int ncb, int halo_total, hipStream_t st) {
-  switch (ntb) {
-    case 1: return launch_ksplit<T, KS, 1>(k, ncb, halo_total, st);
-    case 3: return launch_ksplit<T, KS, 3>(k, ncb, halo_total, st);
-    case 4: return launch_ksplit<T, KS, 4>(k, ncb, halo_total, st);
-    case 5: return launch_ksplit<T, KS, 5>(k, ncb, halo_total, st);
+int dispatch_ksplit(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  switch (p.ntb) {
+    case 1: return launch_ksplit<T, KS, 1>(k, p, st);
+    case 3: return launch_ksplit<T, KS, 3>(k, p, st);
+    case 4: return launch_ksplit<T, KS, 4>(k, p, st);
+    case 5: return launch_ksplit<T, KS, 5>(k, p, st);
   }
-  vmg_set_error("conv (k-split): cout_tiles must be 1, 3, 4 or 5 (got %d)", ntb);
+  vmg_set_error("conv (k-split): cout_tiles must be 1, 3, 4 or 5 (got %d)", p.ntb);
   return -1;
 }
 
 template <int NTB, int NS = 1>
-int launch_linear_wres(const ConvK& k, int ncb, hipStream_t st) {
-  constexpr int WAVE_LDS = 2 * 5 * NS * 1024 + ((EpiLds<NTB>::BYTES + 1023) & ~1023);
-  const int lds = 4 * WAVE_LDS;
+int launch_linear_wres(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  static_assert(wres_lds_bytes(NTB, NS) == 4 * (2 * 5 * NS * 1024 + ((EpiLds<NTB>::BYTES + 1023) & ~1023)), "linear_wres_kernel: LDS");
+  const int lds = p.lds;
   auto fn = linear_wres_kernel<NTB, NS>;
   static bool attr_set[VMG_MAX_DEVICES] = {};
   const int dev = vmg_current_device();
@@ -1986,27 +1997,15 @@ int launch_linear_wres(const ConvK& k, int ncb, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set[dev] = true;
   }
-  const int ncu = vmg_cu_count(dev);
-  const long long ntiles = cdiv64(k.M, 16);
-  VMG_CHECK(ntiles > 0 && ntiles < (1ll << 31), "conv: bad tile count %lld", ntiles);
-  // two workgroups per CU over all output-channel blocks; at least 4 tiles per wave so the resident weights pay off
-  constexpr int WG_PER_CU = NS == 1 ? 2 : 1;
-  long long waves = (long long)(WG_PER_CU * ncu / ncb > 0 ? WG_PER_CU * ncu / ncb : 1) * 4;
-  long long tpw = cdiv64(ntiles, waves);
-  if (tpw < 4) tpw = 4;
-  const long long nwg = cdiv64(cdiv64(ntiles, tpw), 4);
-  hipLaunchKernelGGL(fn, dim3((unsigned)nwg, ncb), dim3(256), lds, st, k, (int)ntiles, (int)tpw);
+  hipLaunchKernelGGL(fn, dim3((unsigned)p.gx, p.gy), dim3(256), lds, st, k, (int)cdiv64(k.M, 16), p.tpw);
   VMG_LAUNCH_CHECK();
   return 0;
 }
 
 template <int NCT, int NB, bool FULL>
-int launch_wstat2(const ConvK& k, int ncb, hipStream_t st) {
-  constexpr int SS = stage_stride(3, NCT, 16);
-  constexpr int HB = ((10 * 18 * 9 + 63) / 64) * 1024;
-  constexpr int lds = 3 * NB * SS + 2 * HB + NCT * 16 * 4 + 128 * (NCT * 64 + 16);
+int launch_wstat2(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  constexpr int lds = wstat_lds_bytes(NCT, NB);
   static_assert(lds <= 160 * 1024, "conv_wstat_kernel: LDS");
-  VMG_CHECK(k.nstages == 3 * NB, "conv (weights-stationary): %d stages in the pack, %d expected", k.nstages, 3 * NB);
   auto fn = conv_wstat_kernel<NCT, NB, FULL>;
   static bool attr_set[VMG_MAX_DEVICES] = {};
   const int dev = vmg_current_device();
@@ -2014,31 +2013,22 @@ int launch_wstat2(const ConvK& k, int ncb, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set[dev] = true;
   }
-  const long long ntiles = (long long)k.N * k.tiles_y * k.tiles_x;
-  VMG_CHECK(ntiles > 0 && ntiles < (1ll << 30), "conv: bad tile count %lld", ntiles);
-  int nwg = vmg_cu_count(dev) & ~7;  // one workgroup per CU, a multiple of the 8 XCDs
-  if (nwg < 8) nwg = 8;
-  while (nwg > 8 && (long long)(nwg >> 3) > cdiv64(ntiles, 8)) nwg -= 8;  // fewer tiles than workgroups
-  hipLaunchKernelGGL(fn, dim3((unsigned)nwg, ncb), dim3(512), lds, st, k, (int)ntiles);
+  hipLaunchKernelGGL(fn, dim3((unsigned)p.gx, p.gy), dim3(512), lds, st, k, (int)((long long)k.N * k.tiles_y * k.tiles_x));
   VMG_LAUNCH_CHECK();
   return 0;
 }
 
 template <int NCT, int NB>
-int launch_wstat(const ConvK& k, int ncb, hipStream_t st) {
-  const bool full = k.res || k.aux || k.out_pre || k.act == VMG_ACT_GELU;
-  return full ? launch_wstat2<NCT, NB, true>(k, ncb, st) : launch_wstat2<NCT, NB, false>(k, ncb, st);
+int launch_wstat(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  return (p.variant >> 4) ? launch_wstat2<NCT, NB, true>(k, p, st) : launch_wstat2<NCT, NB, false>(k, p, st);
 }
 
+// (conv_plan has chosen k.ring)
 template <int NCT>
-int launch_ws(const ConvK& k, int ncb, hipStream_t st) {
+int launch_ws(const ConvK& k, const ConvPlan& p, hipStream_t st) {
   using G = WsGeo<NCT>;
-  ConvK kk = k;
-  // NCT = 3 (48-channel blocks, three workgroups per tile): three ring slots, <= 80 KiB in all, so that TWO workgroups share a CU -- one's halo
-  // burst and store tail run under the other's K loop.  For launches with several tiles per CU (functional.choose_tiling).
-  kk.ring = NCT <= 3 ? 3 : ((k.halo_bytes + 4 * G::STG + G::COB * 4 <= 160 * 1024) ? 4 : 3);
-  const int lds = k.halo_bytes + kk.ring * G::STG + G::COB * 4;
-  VMG_CHECK(lds <= 160 * 1024, "conv (weight-streaming): LDS request %d B exceeds 160 KiB", lds);
+  static_assert(ws_stage_bytes(NCT) == G::STG, "conv_ws_kernel: stage bytes");
+  const int lds = p.lds;
   auto fn = conv_ws_kernel<NCT>;
   static bool attr_set[VMG_MAX_DEVICES] = {};
   const int dev = vmg_current_device();
@@ -2046,10 +2036,8 @@ int launch_ws(const ConvK& k, int ncb, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set[dev] = true;
   }
-  const long long nblk = (long long)k.N * k.tiles_y * k.tiles_x;
-  VMG_CHECK(nblk > 0 && nblk < (1ll << 31), "conv: bad grid %lld", nblk);
   const bool prof = (k.nsrc == 1 && k.src_ch[0] == k.Cout && (k.Cout == 144 || k.Cout == 112)) && vmg_prof_before(VMG_PROF_CONV3X3, k.M, st);
-  hipLaunchKernelGGL(fn, dim3((unsigned)nblk, ncb), dim3(G::THREADS), lds, st, kk);
+  hipLaunchKernelGGL(fn, dim3((unsigned)p.gx, p.gy), dim3(G::THREADS), lds, st, k);
   if (prof) vmg_prof_after(st);
   VMG_LAUNCH_CHECK();
   return 0;
@@ -2242,7 +2230,10 @@ extern "C" int vmg_pack_run(const void* plan_dev, int n, int total_blocks, void*
   return 0;
 }
 
-extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
+// The one place that decides what a vmg_conv_fwd call runs: validates the descriptor, fills the kernel arguments `k` and the plan `p`.
+// Reads the descriptor's pointers only as numbers (null, alignment); with ncu > 0 it makes no device call (ncu = 0: the current device's
+// compute units, asked for only by the two persistent families whose grid depends on them).
+static int conv_plan(const vmg_conv_desc* d, int ncu, ConvK& k, ConvPlan& p) {
   VMG_CHECK(d != nullptr, "conv_fwd: null descriptor");
   VMG_CHECK(d->ks == 1 || d->ks == 3 || d->ks == 7, "conv_fwd: ks must be 1, 3 or 7");
   VMG_CHECK(d->dtype == VMG_F32 || d->dtype == VMG_BF16, "conv_fwd: bad dtype");
@@ -2255,8 +2246,8 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
                 d->deep == VMG_CONV_WSTAT,
             "conv_fwd: unknown kernel route deep = %d", d->deep);
   const int es = d->dtype == VMG_BF16 ? 2 : 4, cbytes = es * 8;
-  ConvK k;
   memset(&k, 0, sizeof(k));
+  memset(&p, 0, sizeof(p));
   short xoff[MAX_ISRC];
   int parent[MAX_ISRC];
   const int n = expand_sources(d->nsrc, nullptr, d->src_ch, xoff, k.src_ch, parent);
@@ -2300,14 +2291,15 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
   }
 #endif
   {
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    auto al = [](const void* ptr) { return ((uintptr_t)ptr & 15) == 0; };
     k.vec8 = d->dtype == VMG_BF16 && !d->pixel_shuffle && (d->Cout % 16) == 0 && (d->out_ps % 8) == 0 && al(d->out) &&
              (!d->out_pre || al(d->out_pre)) && (!d->res || ((d->res_ps % 8) == 0 && al(d->res))) &&
              (!d->aux || ((d->aux_ps % 8) == 0 && al(d->aux)));
   }
   k.nstages = kt; k.halo_bytes = (halo + 1023) & ~1023;  // the LDS-DMA copy writes whole 1-KiB pieces
   VMG_CHECK(d->out_ps >= (d->pixel_shuffle ? d->Cout / 4 : d->Cout), "conv_fwd: out pixel stride too small");
-  hipStream_t st = (hipStream_t)stream;
+  p.dtype = d->dtype; p.ks = d->ks; p.mt = mt; p.ntb = ntb; p.vec8 = k.vec8; p.gy = ncb;
+  auto cus = [&]() { return ncu > 0 ? ncu : vmg_cu_count(vmg_current_device()); };
   if (d->deep == VMG_CONV_WS) {
     // weight-streaming kernel: 8 x 16 pixel tiles, dense halo, its own packed layout (vmg_convws_pack)
     VMG_CHECK(d->dtype == VMG_BF16 && d->ks == 3 && k.vec8 && (ntb == 3 || ntb == 7 || ntb == 8 || ntb == 9), "conv_fwd: the weight-streaming kernel is bf16 3x3 with 16-byte aligned rows, cout_tiles 3, 7, 8 or 9");
@@ -2323,42 +2315,131 @@ extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
     k.nstages = kt3;
     k.halo_bytes = (halo3 + 1023) & ~1023;  // whole 1-KiB LDS-DMA pieces
     k.tiles_y = cdiv(d->H, 8);
-    return ntb == 9 ? launch_ws<9>(k, ncb, st) : (ntb == 7 ? launch_ws<7>(k, ncb, st) : (ntb == 8 ? launch_ws<8>(k, ncb, st) : launch_ws<3>(k, ncb, st)));
+    // NCT = 3 (48-channel blocks, three workgroups per tile): three ring slots, <= 80 KiB in all, so that TWO workgroups share a CU -- one's halo
+    // burst and store tail run under the other's K loop.  For launches with several tiles per CU (functional.choose_tiling).
+    k.ring = ntb <= 3 ? 3 : ((k.halo_bytes + 4 * ws_stage_bytes(ntb) + ntb * 16 * 4 <= 160 * 1024) ? 4 : 3);
+    p.lds = k.halo_bytes + k.ring * ws_stage_bytes(ntb) + ntb * 16 * 4;
+    VMG_CHECK(p.lds <= 160 * 1024, "conv (weight-streaming): LDS request %d B exceeds 160 KiB", p.lds);
+    const long long nblk = (long long)k.N * k.tiles_y * k.tiles_x;
+    VMG_CHECK(nblk > 0 && nblk < (1ll << 31), "conv: bad grid %lld", nblk);
+    p.family = VMG_CONV_FAM_WS; p.gx = (int)nblk;
+    return 0;
   }
   if (d->deep == VMG_CONV_WSTAT && d->dtype == VMG_BF16 && d->ks == 3 && mt == 1 && k.vec8 && n == 1 && (ntb == 1 || ntb == 3 || ntb == 4) && k.src_ch[0] <= 64 && k.src_ch[0] % 8 == 0 &&
       k.src_ps[0] % 8 == 0 && d->W <= 255 * 16 && (long long)d->W * k.src_ps[0] * 2 * 10 < (1ll << 31)) {
     // weights-stationary kernel (a hint: anything it does not cover takes the general kernel below); its tiles are 8 rows high
-    ConvK kk = k;
-    kk.tiles_y = cdiv(d->H, 8);
     const int nb = (k.src_ch[0] / 8 + 3) / 4;  // 32-channel blocks: 1 or 2
-    switch (ntb * 2 + (nb - 1)) {
-      case 2: return launch_wstat<1, 1>(kk, ncb, st);
-      case 3: return launch_wstat<1, 2>(kk, ncb, st);
-      case 6: return launch_wstat<3, 1>(kk, ncb, st);
-      case 7: return launch_wstat<3, 2>(kk, ncb, st);
-      case 8: return launch_wstat<4, 1>(kk, ncb, st);
-      case 9: return launch_wstat<4, 2>(kk, ncb, st);
-    }
+    VMG_CHECK(k.nstages == 3 * nb, "conv (weights-stationary): %d stages in the pack, %d expected", k.nstages, 3 * nb);
+    k.tiles_y = cdiv(d->H, 8);
+    const long long ntiles = (long long)k.N * k.tiles_y * k.tiles_x;
+    VMG_CHECK(ntiles > 0 && ntiles < (1ll << 30), "conv: bad tile count %lld", ntiles);
+    int nwg = cus() & ~7;  // one workgroup per CU, a multiple of the 8 XCDs
+    if (nwg < 8) nwg = 8;
+    while (nwg > 8 && (long long)(nwg >> 3) > cdiv64(ntiles, 8)) nwg -= 8;  // fewer tiles than workgroups
+    const bool full = k.res || k.aux || k.out_pre || k.act == VMG_ACT_GELU;
+    p.family = VMG_CONV_FAM_WSTAT; p.variant = nb | (full ? 16 : 0); p.gx = nwg; p.lds = wstat_lds_bytes(ntb, nb);
+    return 0;
   }
   if (d->deep == VMG_CONV_LINEAR_WRES && d->dtype == VMG_BF16 && d->ks == 1 && k.vec8 && (ntb == 3 || ntb == 5)) {
     // (a hint: anything it does not cover -- padded LDS stride, several sources, unaligned rows -- takes the general kernel below)
-    if (n == 1 && k.src_ch[0] <= 160 && k.src_pixb[0] == k.src_ch[0] * 2) return ntb == 3 ? launch_linear_wres<3>(k, ncb, st) : launch_linear_wres<5>(k, ncb, st);
+    int ns = 0;
+    if (n == 1 && k.src_ch[0] <= 160 && k.src_pixb[0] == k.src_ch[0] * 2) ns = 1;
     // one wide source that the pack split into two equal blocks (288 = 2 x 144)
-    if (n == 2 && ntb == 3 && d->nsrc == 1 && k.src_ch[0] == k.src_ch[1] && k.src_ch[0] <= 160 && k.src[1] == k.src[0] + k.src_ch[0] * 2 &&
-        k.src_nst[0] == k.src_nst[1])
-      return launch_linear_wres<3, 2>(k, ncb, st);
+    else if (n == 2 && ntb == 3 && d->nsrc == 1 && k.src_ch[0] == k.src_ch[1] && k.src_ch[0] <= 160 && k.src[1] == k.src[0] + k.src_ch[0] * 2 &&
+             k.src_nst[0] == k.src_nst[1])
+      ns = 2;
+    if (ns) {
+      const long long ntiles = cdiv64(k.M, 16);
+      VMG_CHECK(ntiles > 0 && ntiles < (1ll << 31), "conv: bad tile count %lld", ntiles);
+      // two workgroups per CU over all output-channel blocks; at least 4 tiles per wave so the resident weights pay off
+      const int wg_per_cu = ns == 1 ? 2 : 1, c = cus();
+      long long waves = (long long)(wg_per_cu * c / ncb > 0 ? wg_per_cu * c / ncb : 1) * 4;
+      long long tpw = cdiv64(ntiles, waves);
+      if (tpw < 4) tpw = 4;
+      p.family = VMG_CONV_FAM_LINEAR_WRES; p.variant = ns; p.gx = (int)cdiv64(cdiv64(ntiles, tpw), 4); p.tpw = (int)tpw; p.lds = wres_lds_bytes(ntb, ns);
+      return 0;
+    }
   }
-  if (d->ks == 7) return d->dtype == VMG_BF16 ? dispatch_ks7<bf16>(k, ntb, ncb, st) : dispatch_ks7<float>(k, ntb, ncb, st);
-  if (d->deep == VMG_CONV_KSPLIT) {
+  const bool ksplit = d->ks != 7 && d->deep == VMG_CONV_KSPLIT;
+  if (ksplit) {
     VMG_CHECK(d->dtype == VMG_BF16 && mt == 1, "conv_fwd: the k-split variant is bf16, mt = 1");
-    return d->ks == 3 ? dispatch_ksplit<bf16, 3>(k, ntb, ncb, k.halo_bytes, st) : dispatch_ksplit<bf16, 1>(k, ntb, ncb, k.halo_bytes, st);
+    if (!(ntb == 1 || ntb == 3 || ntb == 4 || ntb == 5)) {
+      vmg_set_error("conv (k-split): cout_tiles must be 1, 3, 4 or 5 (got %d)", ntb);
+      return -1;
+    }
+    const int scratch = 12 * ntb * 1024;
+    p.lds = (k.halo_bytes > scratch ? k.halo_bytes : scratch) + 16 + ntb * 16 * 4;
+    VMG_CHECK(p.lds <= 160 * 1024, "conv (k-split): LDS request %d B exceeds 160 KiB", p.lds);
+    k.halo_bytes = p.lds - 16 - ntb * 16 * 4;  // zero slot and bias sit behind max(halo, scratch)
+    p.family = VMG_CONV_FAM_KSPLIT;
+  } else {
+    if (d->ks == 7) {
+      if (!(ntb == 1 || ntb == 2 || ntb == 4)) {
+        vmg_set_error("conv (7x7): cout_tiles must be 1, 2 or 4 (got %d)", ntb);
+        return -1;
+      }
+    } else if (!(ntb == 1 || ntb == 3 || ntb == 4 || ntb == 5 || ntb == 7 || ntb == 8 || ntb == 9)) {
+      vmg_set_error("conv: cout_tiles must be 1, 3, 4, 5, 7, 8 or 9 (got %d)", ntb);
+      return -1;
+    }
+    p.lds = k.halo_bytes + 2 * stage_stride(d->ks, ntb, cbytes);  // halo tile + the 2-slot weight ring
+    VMG_CHECK(p.lds <= 160 * 1024, "conv: LDS request %d B exceeds 160 KiB", p.lds);
+    p.family = VMG_CONV_FAM_IGEMM;
   }
-  if (d->dtype == VMG_BF16) {
-    if (d->ks == 3) return mt == 2 ? dispatch_ntb<bf16, 3, 2>(k, ntb, ncb, st) : dispatch_ntb<bf16, 3, 1>(k, ntb, ncb, st);
-    return mt == 2 ? dispatch_ntb<bf16, 1, 2>(k, ntb, ncb, st) : dispatch_ntb<bf16, 1, 1>(k, ntb, ncb, st);
+  const long long nblk = (d->ks > 1) ? (long long)k.N * k.tiles_y * k.tiles_x : cdiv64(k.M, 64 * mt);
+  VMG_CHECK(nblk > 0 && nblk < (1ll << 31), "conv: bad grid %lld", nblk);
+  p.gx = (int)nblk;
+  return 0;
+}
+
+// the template instance that the plan names
+static int conv_launch(const ConvK& k, const ConvPlan& p, hipStream_t st) {
+  switch (p.family) {
+    case VMG_CONV_FAM_WS:
+      return p.ntb == 9 ? launch_ws<9>(k, p, st) : (p.ntb == 7 ? launch_ws<7>(k, p, st) : (p.ntb == 8 ? launch_ws<8>(k, p, st) : launch_ws<3>(k, p, st)));
+    case VMG_CONV_FAM_WSTAT:
+      switch (p.ntb * 2 + ((p.variant & 15) - 1)) {
+        case 2: return launch_wstat<1, 1>(k, p, st);
+        case 3: return launch_wstat<1, 2>(k, p, st);
+        case 6: return launch_wstat<3, 1>(k, p, st);
+        case 7: return launch_wstat<3, 2>(k, p, st);
+        case 8: return launch_wstat<4, 1>(k, p, st);
+        case 9: return launch_wstat<4, 2>(k, p, st);
+      }
+      break;
+    case VMG_CONV_FAM_LINEAR_WRES:
+      if (p.variant == 2) return launch_linear_wres<3, 2>(k, p, st);
+      return p.ntb == 3 ? launch_linear_wres<3>(k, p, st) : launch_linear_wres<5>(k, p, st);
+    case VMG_CONV_FAM_KSPLIT:
+      return p.ks == 3 ? dispatch_ksplit<bf16, 3>(k, p, st) : dispatch_ksplit<bf16, 1>(k, p, st);
+    case VMG_CONV_FAM_IGEMM:
+      if (p.ks == 7) return p.dtype == VMG_BF16 ? dispatch_ks7<bf16>(k, p, st) : dispatch_ks7<float>(k, p, st);
+      if (p.dtype == VMG_BF16) {
+        if (p.ks == 3) return p.mt == 2 ? dispatch_ntb<bf16, 3, 2>(k, p, st) : dispatch_ntb<bf16, 3, 1>(k, p, st);
+        return p.mt == 2 ? dispatch_ntb<bf16, 1, 2>(k, p, st) : dispatch_ntb<bf16, 1, 1>(k, p, st);
+      }
+      if (p.ks == 3) return dispatch_ntb<float, 3, 1>(k, p, st);
+      return dispatch_ntb<float, 1, 1>(k, p, st);
   }
-  if (d->ks == 3) return dispatch_ntb<float, 3, 1>(k, ntb, ncb, st);
-  return dispatch_ntb<float, 1, 1>(k, ntb, ncb, st);
+  vmg_set_error("conv_fwd: no kernel for plan family %d", p.family);
+  return -1;
+}
+
+extern "C" int vmg_conv_fwd(const vmg_conv_desc* d, void* stream) {
+  ConvK k;
+  ConvPlan p;
+  if (conv_plan(d, 0, k, p)) return -1;
+  return conv_launch(k, p, (hipStream_t)stream);
+}
+
+extern "C" int vmg_conv_fwd_plan(const vmg_conv_desc* d, int ncu, int* plan) {
+  VMG_CHECK(plan != nullptr && ncu >= 0, "conv_fwd_plan: null plan / negative ncu");
+  ConvK k;
+  ConvPlan p;
+  if (conv_plan(d, ncu, k, p)) return -1;
+  const int v[VMG_CONV_PLAN_INTS] = {p.family, p.dtype, p.ks, p.mt, p.ntb, p.variant, p.vec8, p.gx, p.gy, p.tpw, p.lds};
+  for (int i = 0; i < VMG_CONV_PLAN_INTS; ++i) plan[i] = v[i];
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ residual chains

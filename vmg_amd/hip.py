@@ -18,6 +18,9 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_GELU = 0, 1, 2, 3
 # conv kernel routes (ConvDesc.deep, include/vmg_hip.h VMG_CONV_*)
 CONV_GENERAL, CONV_KSPLIT, CONV_WS, CONV_LINEAR_WRES, CONV_WSTAT = 0, 2, 3, 4, 6
+# kernel families of vmg_conv_fwd_plan (include/vmg_hip.h VMG_CONV_FAM_*) and the length of its result
+CONV_FAM_IGEMM, CONV_FAM_KSPLIT, CONV_FAM_WS, CONV_FAM_LINEAR_WRES, CONV_FAM_WSTAT = 1, 2, 3, 4, 5
+CONV_PLAN_INTS = 11
 # weight-gradient kernels (vmg_conv_wgrad_last_kernel, include/vmg_hip.h VMG_WGRAD_*)
 WGRAD_V1, WGRAD_3, WGRAD_3B, WGRAD_L2, WGRAD_7 = 1, 2, 3, 4, 5
 
@@ -100,6 +103,7 @@ SIGNATURES = {
     "vmg_convws_pack_bytes": (c_int64, [c_int, c_int, POINTER(c_int), c_int]),
     "vmg_convws_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, c_int, c_void_p, c_void_p]),
     "vmg_conv_fwd": (c_int, [POINTER(ConvDesc), c_void_p]),
+    "vmg_conv_fwd_plan": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int)]),
     "vmg_resblock_chain_fwd": (c_int, [POINTER(ChainDesc), c_void_p]),
     "vmg_resblock_chain_bwd": (c_int, [POINTER(ChainDesc), c_void_p]),
     "vmg_act_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_void_p]),

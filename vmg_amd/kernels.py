@@ -5,6 +5,7 @@ stream.  Shapes are validated on the host before a kernel is launched.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import struct
@@ -175,13 +176,8 @@ def _pix_stride(t: torch.Tensor) -> int:
     return ps
 
 
-def conv_forward(srcs: Sequence[torch.Tensor], pw: PackedConv, bias: Optional[torch.Tensor], N: int, H: int, W: int,
-                 act: int = hip.ACT_NONE, slope: float = 0.0, alpha: float = 1.0, res: Optional[torch.Tensor] = None,
-                 aux: Optional[torch.Tensor] = None, actgrad: int = 0, pixel_shuffle: bool = False,
-                 out: Optional[torch.Tensor] = None, out_pre: Optional[torch.Tensor] = None, want_pre: bool = False,
-                 mt: int = 0, deep: int = hip.CONV_GENERAL) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-    """Runs vmg_conv_fwd.  srcs: channels-last tensors (..., C_s) covering N*H*W pixels each (channel slices of
-    wider tensors are fine).  Returns (out, out_pre)."""
+def _conv_fill(srcs, pw, bias, N, H, W, act, slope, alpha, res, aux, actgrad, pixel_shuffle, out, out_pre, want_pre, mt, deep):
+    """Validates a conv_forward call and fills the shared descriptor; returns (descriptor, out, out_pre)."""
     if len(srcs) != len(pw.src_ch):
         raise HipError(f"conv expects {len(pw.src_ch)} sources, got {len(srcs)}")
     x0 = srcs[0]
@@ -235,8 +231,35 @@ def conv_forward(srcs: Sequence[torch.Tensor], pw: PackedConv, bias: Optional[to
     _CONV_PACK(d, 0, hip.dtype_code(dt), pw.ks, pw.cout_tiles, N, H, W, pw.cout, nsrc, sp[0], sp[1], sp[2], sp[3], sps[0], sps[1], sps[2], sps[3],
                sch[0], sch[1], sch[2], sch[3], pw.buf.data_ptr(), bias_p, out.data_ptr(), out_ps, pre_p, extra[0], extra[1], extra[2], extra[3],
                act, slope, alpha, actgrad, int(pixel_shuffle), mt, deep)
+    return d, out, out_pre
+
+
+def conv_forward(srcs: Sequence[torch.Tensor], pw: PackedConv, bias: Optional[torch.Tensor], N: int, H: int, W: int,
+                 act: int = hip.ACT_NONE, slope: float = 0.0, alpha: float = 1.0, res: Optional[torch.Tensor] = None,
+                 aux: Optional[torch.Tensor] = None, actgrad: int = 0, pixel_shuffle: bool = False,
+                 out: Optional[torch.Tensor] = None, out_pre: Optional[torch.Tensor] = None, want_pre: bool = False,
+                 mt: int = 0, deep: int = hip.CONV_GENERAL) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Runs vmg_conv_fwd.  srcs: channels-last tensors (..., C_s) covering N*H*W pixels each (channel slices of
+    wider tensors are fine).  Returns (out, out_pre)."""
+    d, out, out_pre = _conv_fill(srcs, pw, bias, N, H, W, act, slope, alpha, res, aux, actgrad, pixel_shuffle, out, out_pre, want_pre, mt, deep)
     hip.check(hip.lib().vmg_conv_fwd(ctypes.byref(d), hip.stream_ptr()), "vmg_conv_fwd")
     return out, out_pre
+
+
+ConvPlan = collections.namedtuple("ConvPlan", "family dtype ks mt ntb variant vec8 grid_x grid_y tiles_per_wave lds_bytes")
+
+
+def conv_forward_plan(srcs: Sequence[torch.Tensor], pw: PackedConv, bias: Optional[torch.Tensor], N: int, H: int, W: int,
+                      act: int = hip.ACT_NONE, slope: float = 0.0, alpha: float = 1.0, res: Optional[torch.Tensor] = None,
+                      aux: Optional[torch.Tensor] = None, actgrad: int = 0, pixel_shuffle: bool = False,
+                      out: Optional[torch.Tensor] = None, out_pre: Optional[torch.Tensor] = None, want_pre: bool = False,
+                      mt: int = 0, deep: int = hip.CONV_GENERAL, ncu: int = 0) -> ConvPlan:
+    """What conv_forward would launch for the same arguments (vmg_conv_fwd_plan; nothing is enqueued): the kernel family
+    (hip.CONV_FAM_*), its template arguments, the epilogue flavour, the grid and the LDS size.  ncu = 0: the current device's compute units."""
+    d, _, _ = _conv_fill(srcs, pw, bias, N, H, W, act, slope, alpha, res, aux, actgrad, pixel_shuffle, out, out_pre, want_pre, mt, deep)
+    plan = (ctypes.c_int * hip.CONV_PLAN_INTS)()
+    hip.check(hip.lib().vmg_conv_fwd_plan(ctypes.byref(d), ncu, plan), "vmg_conv_fwd_plan")
+    return ConvPlan(*plan)
 
 
 def _parr(ts):
