@@ -13,31 +13,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.q8_ref import quant_emul as _quant_emul, wquant_emul as _wquant_emul  # (the kernel's own tests: tests/test_conv_q8_kernels_gpu.py)
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def _quant_emul(x):
-    """torch emulation of the record quantiser: x (..., C) fp32 -> dequantised fp32 of the same shape."""
-    C = x.shape[-1]
-    nb = (C + 31) // 32
-    xp = F.pad(x, (0, nb * 32 - C)).reshape(*x.shape[:-1], nb, 32)
-    amax = xp.abs().amax(-1, keepdim=True)
-    bits = amax.view(torch.int32)
-    sb = ((bits >> 23) & 255) - 8 + ((bits & 0x7FFFFF) > 0x600000).int()
-    sb = sb.clamp(1, 254)
-    mult = torch.exp2(127.0 - sb.float())
-    q = (xp * mult).to(torch.float8_e4m3fn).float() / mult
-    return q.reshape(*x.shape[:-1], nb * 32)[..., :C]
-
-
-def _wquant_emul(w):
-    """per-output-channel power-of-two scale, e4m3 values: (O, I, 3, 3) fp32 -> dequantised fp32."""
-    amax = w.abs().amax((1, 2, 3), keepdim=True)
-    bits = amax.view(torch.int32)
-    sb = (((bits >> 23) & 255) - 8 + ((bits & 0x7FFFFF) > 0x600000).int()).clamp(1, 254)
-    mult = torch.exp2(127.0 - sb.float())
-    return (w * mult).to(torch.float8_e4m3fn).float() / mult
 
 
 @pytest.mark.parametrize("C", [144, 112])

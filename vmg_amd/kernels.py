@@ -1401,21 +1401,24 @@ _Q8_DESC = hip.ConvQ8Desc()
 
 def conv_q8_forward(src: torch.Tensor, pw: PackedQ8, bias: Optional[torch.Tensor], N: int, H: int, W: int, act: int = hip.ACT_NONE,
                     slope: float = 0.0, alpha: float = 1.0, res: Optional[torch.Tensor] = None, want_bf16: bool = True, want_q8: bool = True,
-                    out: Optional[torch.Tensor] = None):
-    """[res +] alpha * act(conv3x3(src records) + bias) -> (bf16 (N,H,W,Cout) or None, records (N,H,W,rec) or None) (vmg_convq8_fwd)."""
-    hip.require_cuda(src, bias, res, out)
-    rec_in = q8_record_bytes(pw.cin)
+                    out: Optional[torch.Tensor] = None, outq: Optional[torch.Tensor] = None):
+    """[res +] alpha * act(conv3x3(src records) + bias) -> (bf16 (N,H,W,Cout) or None, records (N,H,W,rec) or None) (vmg_convq8_fwd).
+    out / outq: the caller's bf16 rows / contiguous record buffer, used instead of a fresh allocation."""
+    hip.require_cuda(src, bias, res, out, outq)
+    rec_in, rec_out = q8_record_bytes(pw.cin), q8_record_bytes(pw.cout)
     if src.dtype != torch.uint8 or not src.is_contiguous() or src.shape[-1] != rec_in or src.numel() != N * H * W * rec_in:
         raise HipError(f"conv_q8: contiguous uint8 records (N*H*W, {rec_in}) expected, got {tuple(src.shape)}")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != pw.cout or not bias.is_contiguous()):
         raise HipError("conv_q8: bias must be contiguous fp32 of length Cout")
     if res is not None and (res.dtype != torch.bfloat16 or res.shape[-1] != pw.cout or res.numel() // pw.cout != N * H * W):
         raise HipError("conv_q8: the residual must be a bf16 tensor of the output's shape")
+    if outq is not None and (outq.dtype != torch.uint8 or not outq.is_contiguous() or outq.shape[-1] != rec_out or outq.numel() != N * H * W * rec_out):
+        raise HipError(f"conv_q8: outq must be contiguous uint8 records (N*H*W, {rec_out}), got {tuple(outq.shape)}")
     o = oq = None
     if want_bf16:
         o = out if out is not None else torch.empty((N, H, W, pw.cout), dtype=torch.bfloat16, device=src.device)
     if want_q8:
-        oq = torch.empty((N, H, W, q8_record_bytes(pw.cout)), dtype=torch.uint8, device=src.device)
+        oq = outq if outq is not None else torch.empty((N, H, W, rec_out), dtype=torch.uint8, device=src.device)
     d = _Q8_DESC
     d.N, d.H, d.W, d.Cin, d.Cout = N, H, W, pw.cin, pw.cout
     d.src, d.packed, d.bias = src.data_ptr(), pw.buf.data_ptr(), bias.data_ptr() if bias is not None else None
