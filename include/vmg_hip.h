@@ -440,6 +440,36 @@ int vmg_ltam_bwd_tab(int dtype, const void* q, const void* const* keys, const vo
                      void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Hard trajectory attention = LTAM_multi_head.forward_max without the output projection (models/trajectory.py:550-670,
+ * en_field=False, if_ia=False): traj_mode 'max'.  Tensors as above, no windows: h and w are arbitrary.
+ *   For pixel p and key-frame j: s_j = the nearest-neighbour source pixel of loc (zeros padding, align_corners=True, fp32, the
+ *   arithmetic of the window mode's gather); K_j = keys[j][s_j], the zero row when s_j lies outside the map.
+ *   qn = q / max(||q||, 1e-12), kn_j = K_j / max(||K_j||, 1e-12): both norms over ALL c channels, before the head split.
+ *   For head g (channels g*D .. g*D+D, D = c / 4): score[g][j] = <qn_g, kn_{j,g}> (scale 1; exactly 0 without a source);
+ *   idx[g] = the FIRST j attaining max_j score[g][j]; sc[g] = that maximum; out_g = sc[g] * vals[idx[g]][s_idx[g]]_g (0 without a source).
+ *   out (n,h,w,c); idx (n,h,w,heads) int32; score (n,h,w,heads) fp32 = sc.
+ * Backward: idx is an INPUT, never re-decided (an entry outside 0..t-1 selects nothing).  With V = vals[idx[g]][s]_g, gs[g] = <dout_g, V>:
+ *   dV = sc[g] * dout_g, added to dv_acc[idx[g]] at row s, slice g;
+ *   dqn_g = gs[g] * kn_{idx[g],g};  dq = (dqn - qn <qn, dqn>) / max(||q||, eps) over all c;
+ *   dkn (slice g only) = gs[g] * qn_g;  dK = (dkn - kn <kn, dkn>) / ||K||: a row DENSE over all c channels, added to dk_acc[idx[g]] at row s.
+ * sc and kn are recomputed from q and the selected key row.  A selection without a source scatters nothing and gives dq = 0; a key-frame no
+ * pixel selected receives no atomics.  dk_acc / dv_acc: FP32 accumulators as above (caller-zeroed or holding earlier sums).  loc has no gradient.
+ * heads must be 4, head dims 4, 8, 28, 36.  vmg_ltam_max_fwd / _bwd carry the key-frame pointers in the kernel arguments (t <= 32, a 33rd is
+ * refused); the _tab entries read them from the device table in `ws` (vmg_ltam_tab_bytes(t), filled on the stream as above: any t >= 1,
+ * capturable) and run the same kernels: same bits.  Every check precedes every launch.
+ * ---------------------------------------------------------------------------------------------- */
+int vmg_ltam_max_fwd(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, void* out, int* idx,
+                     float* score, int n, int h, int w, int c, int heads, int t, void* stream);
+int vmg_ltam_max_bwd(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const int* idx,
+                     const void* dout, void* dq, void* const* dk_acc, void* const* dv_acc, int n, int h, int w, int c, int heads, int t,
+                     void* stream);
+int vmg_ltam_max_fwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, void* out, int* idx,
+                         float* score, int n, int h, int w, int c, int heads, int t, void* ws, int64_t ws_bytes, void* stream);
+int vmg_ltam_max_bwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const int* idx,
+                         const void* dout, void* dq, void* const* dk_acc, void* const* dv_acc, int n, int h, int w, int c, int heads, int t,
+                         void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Live kernel timing (bench.py roofline object): HIP events are recorded on the launch stream around every
  * `stride`-th launch of kernel class `klass` (1 = bf16 conv3x3 144->144, the trajectory-chain kernel, forward
  * and data-gradient alike) until `max_samples` pairs are used.  vmg_prof_end synchronises those events and

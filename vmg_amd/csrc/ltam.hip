@@ -617,3 +617,403 @@ extern "C" int vmg_ltam_bwd_tab(int dtype, const void* q, const void* const* key
   if (int rc = fill_table(k, keys, vals, dk_acc, dv_acc, t, ws, ws_bytes, (hipStream_t)stream)) return rc;
   return dtype == VMG_BF16 ? dispatch_d<bf16, LtamTabK>(k, true, (hipStream_t)stream) : dispatch_d<float, LtamTabK>(k, true, (hipStream_t)stream);
 }
+
+// =====================================================================================================================================
+// Hard trajectory attention (LTAM_multi_head.forward_max, models/trajectory.py:550-670, en_field=False, if_ia=False), mode 'max'.
+//
+// Per pixel and head g: score[g][j] = <qn_g, kn_{j,g}> over the t key-frames (q and the gathered key rows L2-normalised over ALL c channels,
+// eps 1e-12, scale 1; a key-frame whose tracked position lies outside the map scores exactly 0), idx[g] = the FIRST j attaining the maximum,
+// out_g = score[g][idx[g]] * vals[idx[g]][source]_g.  No windows, no softmax: the forward gathers key rows only, key-frame by key-frame, keeps
+// a running first-maximum (strict >) and the address of the winner's value slice, and reads that one slice at the end.  The backward takes
+// idx as given and touches, per pixel, only the (at most four) key-frames its heads selected.
+//
+// Same tile and thread mapping as the window kernels above: 8x8 pixels, 256 threads, thread = pixel * 4 + head.
+namespace {
+
+struct LtmaxK {
+  const char* q;
+  const char* k[LT_MAX_T];
+  const char* v[LT_MAX_T];
+  const float* loc;  // (n, 2t, h, w)
+  char* out;         // (n,h,w,c)
+  int* idx;          // (n,h,w,heads) selected key-frame (written by the forward, read by the backward)
+  float* score;      // (n,h,w,heads) its score
+  // backward
+  const char* dout;
+  char* dq;
+  void* dk_acc[LT_MAX_T];  // (n,h,w,c) fp32 accumulators
+  void* dv_acc[LT_MAX_T];
+  int n, h, w, c, t;
+  int tiles_x, tiles_y;
+};
+struct LtmaxTabK : LtmaxK {
+  void* const* tab;  // [LT_TAB_SETS][t], as LtamTabK::tab
+};
+template <typename A>
+constexpr bool ltmax_is_tab = std::is_same<A, LtmaxTabK>::value;
+
+// what a slice load reads when its row has no source: the widest slice is 36 fp32 channels
+__device__ __attribute__((aligned(16))) unsigned int g_ltmax_zero[36] = {};
+
+template <typename T, int D, typename A>
+__global__ __launch_bounds__(256) void ltam_max_fwd_kernel(const A a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int c = LT_HEADS * D, RS = c + 16 / sizeof(T);
+  T* qt = reinterpret_cast<T*>(smem);
+  T* kt = qt + LT_PIX * RS;
+  int* sidx = reinterpret_cast<int*>(kt + LT_PIX * RS);
+  int* selfidx = sidx + LT_PIX;
+
+  const int tid = threadIdx.x, p = tid >> 2, hd = tid & 3;
+  const int tyi = p >> 3, txi = p & 7;
+  int bid = blockIdx.x;
+  const int tx = bid % a.tiles_x;
+  bid /= a.tiles_x;
+  const int ty = bid % a.tiles_y, n = bid / a.tiles_y;
+  const int y = ty * LT_TILE + tyi, x = tx * LT_TILE + txi;
+  const bool inside = y < a.h && x < a.w;
+  const long long img = (long long)n * a.h * a.w;
+  if (tid < LT_PIX) {
+    const int yy = ty * LT_TILE + (tid >> 3), xx = tx * LT_TILE + (tid & 7);
+    selfidx[tid] = (yy < a.h && xx < a.w) ? yy * a.w + xx : -1;
+  }
+  __syncthreads();
+  RowCopy<T, D> rk;
+  rk.fetch(reinterpret_cast<const T*>(a.q) + img * c, selfidx, tid);
+  rk.store(qt, RS, tid);
+  __syncthreads();
+  float qs[D];  // normalised query slice (scale 1 in this mode)
+  {
+    float ss = 0.f;
+    load_slice<T, D>(qt + p * RS + hd * D, qs);
+#pragma unroll
+    for (int d = 0; d < D; ++d) ss += qs[d] * qs[d];
+    const float inv = 1.f / fmaxf(sqrtf(quad_sum(ss)), 1e-12f);
+#pragma unroll
+    for (int d = 0; d < D; ++d) qs[d] *= inv;
+  }
+  float best = 0.f;
+  int bi = 0;
+  const T* bv = reinterpret_cast<const T*>(g_ltmax_zero);  // the winner's value slice (the zero vector when it has no source)
+  for (int j = 0; j < a.t; ++j) {
+    __syncthreads();  // the previous key-frame's tile and indices are no longer read
+    if (tid < LT_PIX) {
+      int s = -1;
+      if (selfidx[tid] >= 0) {
+        const long long lb = ((long long)n * 2 * a.t + 2 * j) * a.h * a.w + selfidx[tid];
+        s = nearest_index(a.loc[lb], a.loc[lb + (long long)a.h * a.w], a.w, a.h);
+      }
+      sidx[tid] = s;
+    }
+    __syncthreads();
+    const T* kj;
+    const T* vj;
+    if constexpr (ltmax_is_tab<A>) {
+      kj = reinterpret_cast<const T*>(a.tab[j]);
+      vj = reinterpret_cast<const T*>(a.tab[a.t + j]);
+    } else {
+      kj = reinterpret_cast<const T*>(a.k[j]);
+      vj = reinterpret_cast<const T*>(a.v[j]);
+    }
+    rk.fetch(kj + img * c, sidx, tid);
+    rk.store(kt, RS, tid);
+    __syncthreads();
+    float s2 = 0.f, dot = 0.f, kk[D];
+    load_slice<T, D>(kt + p * RS + hd * D, kk);
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      s2 += kk[d] * kk[d];
+      dot += qs[d] * kk[d];
+    }
+    const float score = dot / fmaxf(sqrtf(quad_sum(s2)), 1e-12f);  // (a row without a source: 0 / eps = 0 exactly)
+    const int s = sidx[p];
+    if (j == 0 || score > best) {  // strict: on a tie the earlier key-frame stays
+      best = score;
+      bi = j;
+      bv = s >= 0 ? vj + (img + s) * c + hd * D : reinterpret_cast<const T*>(g_ltmax_zero);
+    }
+  }
+  float vv[D];
+  load_slice<T, D>(bv, vv);
+  if (inside) {
+    const long long px = img + (long long)y * a.w + x;
+    T* o = reinterpret_cast<T*>(a.out) + px * c + hd * D;
+#pragma unroll
+    for (int d = 0; d < D; ++d) o[d] = from_f32<T>(best * vv[d]);
+    a.idx[px * LT_HEADS + hd] = bi;
+    a.score[px * LT_HEADS + hd] = best;
+  }
+}
+
+// Backward, idx given.  Four rounds, one per head g: the 64 pixels' key rows of the key-frame head g selected are staged (per-pixel base pointers:
+// the pixels of a tile select different key-frames), the row is normalised, sc = <qn_g, kn_g> and gs = <dout_g, V_g> are recomputed by the thread of
+// head g and broadcast to its pixel's four threads, and
+//   dV slice g   = sc * dout_g                                     -> key-frame idx[g]'s value accumulator, row s
+//   dK row (all c channels) = (dkn - kn <kn, dkn>) / ||K||,  dkn = gs * qn_g in slice g, 0 elsewhere, <kn, dkn> = gs * sc  -> its key accumulator, row s
+//   dqn_g        = gs * kn_g
+// Both scatters go through LDS so that a wave's atomics run along channels.  A selection without a source (s < 0) has a null row pointer: zero row,
+// gs = 0, nothing scattered.
+template <typename T, int D, typename A>
+__global__ __launch_bounds__(256) void ltam_max_bwd_kernel(const A a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int c = LT_HEADS * D, RS = c + 16 / sizeof(T);
+  constexpr int VN = 16 / sizeof(T), NVEC = c / VN, TOTAL = LT_PIX * NVEC, NIT = (TOTAL + 255) / 256;
+  T* kt = reinterpret_cast<T*>(smem);
+  float* rowbuf = reinterpret_cast<float*>(kt + LT_PIX * RS);  // [64][c] dK rows
+  float* vbuf = rowbuf + LT_PIX * c;                           // [64][D] dV slices
+  const char** kptr = reinterpret_cast<const char**>(vbuf + LT_PIX * D);  // per pixel: the selected key row, value slice, and their accumulators
+  const char** vptr = kptr + LT_PIX;
+  float** dkptr = reinterpret_cast<float**>(const_cast<char**>(vptr + LT_PIX));
+  float** dvptr = dkptr + LT_PIX;
+
+  const int tid = threadIdx.x, p = tid >> 2, hd = tid & 3;
+  const int tyi = p >> 3, txi = p & 7;
+  int bid = blockIdx.x;
+  const int tx = bid % a.tiles_x;
+  bid /= a.tiles_x;
+  const int ty = bid % a.tiles_y, n = bid / a.tiles_y;
+  const int y = ty * LT_TILE + tyi, x = tx * LT_TILE + txi;
+  const bool inside = y < a.h && x < a.w;
+  const long long img = (long long)n * a.h * a.w;
+  const long long px = img + (long long)(inside ? y * a.w + x : 0);
+  const T* zero = reinterpret_cast<const T*>(g_ltmax_zero);
+
+  float qn[D], go[D], dqn[D];
+  load_slice<T, D>(inside ? reinterpret_cast<const T*>(a.q) + px * c + hd * D : zero, qn);
+  load_slice<T, D>(inside ? reinterpret_cast<const T*>(a.dout) + px * c + hd * D : zero, go);
+  float qnorm;
+  {
+    float ss = 0.f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) ss += qn[d] * qn[d];
+    qnorm = fmaxf(sqrtf(quad_sum(ss)), 1e-12f);
+    const float inv = 1.f / qnorm;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      qn[d] *= inv;
+      dqn[d] = 0.f;
+    }
+  }
+  for (int g = 0; g < LT_HEADS; ++g) {
+    __syncthreads();  // the previous round's scatters are done with the pointers and the buffers
+    if (tid < LT_PIX) {
+      const int yy = ty * LT_TILE + (tid >> 3), xx = tx * LT_TILE + (tid & 7);
+      const char *kp = nullptr, *vp = nullptr;
+      float *dkp = nullptr, *dvp = nullptr;
+      if (yy < a.h && xx < a.w) {
+        const int self = yy * a.w + xx;
+        const int bi = a.idx[(img + self) * LT_HEADS + g];
+        if (bi >= 0 && bi < a.t) {  // (an index outside the key-frame list selects nothing)
+          const long long lb = ((long long)n * 2 * a.t + 2 * bi) * a.h * a.w + self;
+          const int s = nearest_index(a.loc[lb], a.loc[lb + (long long)a.h * a.w], a.w, a.h);
+          if (s >= 0) {
+            const void *kb = nullptr, *vb = nullptr;
+            void *dkb = nullptr, *dvb = nullptr;
+            if constexpr (ltmax_is_tab<A>) {
+              kb = a.tab[bi]; vb = a.tab[a.t + bi]; dkb = a.tab[2 * a.t + bi]; dvb = a.tab[3 * a.t + bi];
+            } else {
+              for (int j = 0; j < a.t; ++j)
+                if (j == bi) { kb = a.k[j]; vb = a.v[j]; dkb = a.dk_acc[j]; dvb = a.dv_acc[j]; }
+            }
+            const long long row = (img + s) * c;
+            kp = reinterpret_cast<const char*>(reinterpret_cast<const T*>(kb) + row);
+            vp = reinterpret_cast<const char*>(reinterpret_cast<const T*>(vb) + row + g * D);
+            dkp = reinterpret_cast<float*>(dkb) + row;
+            dvp = reinterpret_cast<float*>(dvb) + row + g * D;
+          }
+        }
+      }
+      kptr[tid] = kp; vptr[tid] = vp; dkptr[tid] = dkp; dvptr[tid] = dvp;
+    }
+    __syncthreads();
+    {  // the 64 key rows, every load unconditional and ahead of the LDS stores (RowCopy, with a base pointer per pixel)
+      lt_u32x4 r[NIT];
+#pragma unroll
+      for (int k = 0; k < NIT; ++k) {
+        const int i = tid + k * 256;
+        const int pp = min(i / NVEC, LT_PIX - 1), v = i - (i / NVEC) * NVEC;
+        const char* rp = kptr[pp];
+        const T* src = (i < TOTAL && rp) ? reinterpret_cast<const T*>(rp) + v * VN : zero;
+        r[k] = *reinterpret_cast<const lt_u32x4*>(src);
+      }
+      float vv[D];
+      const char* vp = vptr[p];
+      load_slice<T, D>((hd == g && vp) ? reinterpret_cast<const T*>(vp) : zero, vv);
+#pragma unroll
+      for (int k = 0; k < NIT; ++k) {
+        const int i = tid + k * 256;
+        const int pp = i / NVEC, v = i - pp * NVEC;
+        if (i < TOTAL) *reinterpret_cast<lt_u32x4*>(kt + pp * RS + v * VN) = r[k];
+      }
+      __syncthreads();
+      float kn[D], s2 = 0.f;
+      load_slice<T, D>(kt + p * RS + hd * D, kn);
+#pragma unroll
+      for (int d = 0; d < D; ++d) s2 += kn[d] * kn[d];
+      const float knorm = fmaxf(sqrtf(quad_sum(s2)), 1e-12f);
+      const float inv = 1.f / knorm;
+      float sc = 0.f, gs = 0.f;
+#pragma unroll
+      for (int d = 0; d < D; ++d) {
+        kn[d] *= inv;
+        sc += qn[d] * kn[d];
+        gs += go[d] * vv[d];
+      }
+      // head g's thread holds sc and gs: to the pixel's four threads
+      const int src_lane = (threadIdx.x & 63 & ~3) | g;
+      sc = __shfl(sc, src_lane, 64);
+      gs = __shfl(gs, src_lane, 64);
+      const float nd = gs * sc;  // <kn, dkn>
+#pragma unroll
+      for (int d = 0; d < D; ++d) rowbuf[p * c + hd * D + d] = ((hd == g ? gs * qn[d] : 0.f) - kn[d] * nd) * inv;
+      if (hd == g) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          vbuf[p * D + d] = sc * go[d];
+          dqn[d] = gs * kn[d];
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < LT_PIX * c; i += 256) {
+      const int pp = i / c, ch = i - pp * c;
+      float* dst = dkptr[pp];
+      if (dst) atomicAdd(dst + ch, rowbuf[i]);
+    }
+    for (int i = tid; i < LT_PIX * D; i += 256) {
+      const int pp = i / D, ch = i - pp * D;
+      float* dst = dvptr[pp];
+      if (dst) atomicAdd(dst + ch, vbuf[i]);
+    }
+  }
+  {  // query normalisation Jacobian
+    float nd = 0.f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) nd += qn[d] * dqn[d];
+    nd = quad_sum(nd);
+    if (inside) {
+      const float inv = 1.f / qnorm;
+      T* dq = reinterpret_cast<T*>(a.dq) + px * c + hd * D;
+#pragma unroll
+      for (int d = 0; d < D; ++d) dq[d] = from_f32<T>((dqn[d] - qn[d] * nd) * inv);
+    }
+  }
+}
+
+template <typename T, int D, typename A>
+int launch_ltmax(const A& k, bool backward, hipStream_t st) {
+  const int RS = k.c + 16 / (int)sizeof(T);
+  const int grid = k.n * k.tiles_y * k.tiles_x;
+  const int dev = vmg_current_device();
+  if (!backward) {
+    const int lds = 2 * LT_PIX * RS * (int)sizeof(T) + 2 * LT_PIX * 4;
+    auto fn = ltam_max_fwd_kernel<T, D, A>;
+    static bool set[VMG_MAX_DEVICES] = {};  // the attribute is per device
+    if (!set[dev]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set[dev] = true; }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, st, k);
+  } else {
+    // (fp32, 144 channels: 37 888 + 36 864 + 9 216 + 2 048 B -- one workgroup per CU less than bf16's 56 KiB allows)
+    const int lds = LT_PIX * RS * (int)sizeof(T) + LT_PIX * (k.c + D) * 4 + 4 * LT_PIX * 8;
+    auto fn = ltam_max_bwd_kernel<T, D, A>;
+    static bool set[VMG_MAX_DEVICES] = {};
+    if (!set[dev]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); set[dev] = true; }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, st, k);
+  }
+  VMG_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename T, typename A>
+int dispatch_ltmax(const A& k, bool backward, hipStream_t st) {
+  switch (k.c / LT_HEADS) {
+    case 4: return launch_ltmax<T, 4, A>(k, backward, st);
+    case 8: return launch_ltmax<T, 8, A>(k, backward, st);
+    case 28: return launch_ltmax<T, 28, A>(k, backward, st);
+    case 36: return launch_ltmax<T, 36, A>(k, backward, st);
+  }
+  vmg_set_error("ltam_max: head dim %d not instantiated (supported: 4, 8, 28, 36)", k.c / LT_HEADS);
+  return -1;
+}
+
+// the checks of both routes and both directions, before any launch (the table route's fill kernels included)
+int fill_ltmax(LtmaxK& k, int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, int n, int h, int w, int c, int heads,
+               int t, bool tab) {
+  VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "ltam_max: bad dtype");
+  VMG_CHECK(q && keys && vals && loc, "ltam_max: null pointer");
+  VMG_CHECK(heads == LT_HEADS, "ltam_max: heads must be %d", LT_HEADS);
+  if (tab) VMG_CHECK(t >= 1, "ltam_max: at least one key-frame");
+  else VMG_CHECK(t >= 1 && t <= LT_MAX_T, "ltam_max: 1..%d key-frames", LT_MAX_T);
+  VMG_CHECK(n > 0 && h > 0 && w > 0 && c > 0 && c % LT_HEADS == 0, "ltam_max: bad shape");
+  VMG_CHECK((long long)n * h * w * c < (1LL << 40), "ltam_max: tensor too large");
+  const int D = c / LT_HEADS;
+  VMG_CHECK(D == 4 || D == 8 || D == 28 || D == 36, "ltam_max: head dim %d not instantiated (supported: 4, 8, 28, 36)", D);
+  memset(&k, 0, sizeof(k));
+  k.q = (const char*)q;
+  for (int j = 0; j < t; ++j) {
+    VMG_CHECK(keys[j] && vals[j], "ltam_max: null key/value %d", j);
+    if (tab) continue;  // (the table holds them)
+    k.k[j] = (const char*)keys[j];
+    k.v[j] = (const char*)vals[j];
+  }
+  k.loc = loc;
+  k.n = n; k.h = h; k.w = w; k.c = c; k.t = t;
+  k.tiles_x = cdiv(w, LT_TILE); k.tiles_y = cdiv(h, LT_TILE);
+  return 0;
+}
+
+int table_ltmax(LtmaxTabK& k, const void* const* keys, const void* const* vals, void* const* dk_acc, void* const* dv_acc, int t, void* ws, int64_t ws_bytes,
+                hipStream_t st) {
+  LtamTabK f;  // (fill_table only sets .tab)
+  f.tab = nullptr;
+  if (int rc = fill_table(f, keys, vals, dk_acc, dv_acc, t, ws, ws_bytes, st)) return rc;
+  k.tab = f.tab;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int vmg_ltam_max_fwd(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, void* out, int* idx,
+                                float* score, int n, int h, int w, int c, int heads, int t, void* stream) {
+  LtmaxK k;
+  if (int rc = fill_ltmax(k, dtype, q, keys, vals, loc, n, h, w, c, heads, t, false)) return rc;
+  VMG_CHECK(out && idx && score, "ltam_max_fwd: null output");
+  k.out = (char*)out; k.idx = idx; k.score = score;
+  return dtype == VMG_BF16 ? dispatch_ltmax<bf16, LtmaxK>(k, false, (hipStream_t)stream) : dispatch_ltmax<float, LtmaxK>(k, false, (hipStream_t)stream);
+}
+
+extern "C" int vmg_ltam_max_bwd(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const int* idx,
+                                const void* dout, void* dq, void* const* dk_acc, void* const* dv_acc, int n, int h, int w, int c, int heads, int t,
+                                void* stream) {
+  LtmaxK k;
+  if (int rc = fill_ltmax(k, dtype, q, keys, vals, loc, n, h, w, c, heads, t, false)) return rc;
+  VMG_CHECK(idx && dout && dq && dk_acc && dv_acc, "ltam_max_bwd: null pointer");
+  k.idx = const_cast<int*>(idx); k.dout = (const char*)dout; k.dq = (char*)dq;
+  for (int j = 0; j < t; ++j) {
+    VMG_CHECK(dk_acc[j] && dv_acc[j], "ltam_max_bwd: null accumulator %d", j);
+    k.dk_acc[j] = dk_acc[j];
+    k.dv_acc[j] = dv_acc[j];
+  }
+  return dtype == VMG_BF16 ? dispatch_ltmax<bf16, LtmaxK>(k, true, (hipStream_t)stream) : dispatch_ltmax<float, LtmaxK>(k, true, (hipStream_t)stream);
+}
+
+extern "C" int vmg_ltam_max_fwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, void* out, int* idx,
+                                    float* score, int n, int h, int w, int c, int heads, int t, void* ws, int64_t ws_bytes, void* stream) {
+  LtmaxTabK k;
+  if (int rc = fill_ltmax(k, dtype, q, keys, vals, loc, n, h, w, c, heads, t, true)) return rc;
+  VMG_CHECK(out && idx && score, "ltam_max_fwd_tab: null output");
+  k.out = (char*)out; k.idx = idx; k.score = score;
+  if (int rc = table_ltmax(k, keys, vals, nullptr, nullptr, t, ws, ws_bytes, (hipStream_t)stream)) return rc;
+  return dtype == VMG_BF16 ? dispatch_ltmax<bf16, LtmaxTabK>(k, false, (hipStream_t)stream) : dispatch_ltmax<float, LtmaxTabK>(k, false, (hipStream_t)stream);
+}
+
+extern "C" int vmg_ltam_max_bwd_tab(int dtype, const void* q, const void* const* keys, const void* const* vals, const float* loc, const int* idx,
+                                    const void* dout, void* dq, void* const* dk_acc, void* const* dv_acc, int n, int h, int w, int c, int heads, int t,
+                                    void* ws, int64_t ws_bytes, void* stream) {
+  LtmaxTabK k;
+  if (int rc = fill_ltmax(k, dtype, q, keys, vals, loc, n, h, w, c, heads, t, true)) return rc;
+  VMG_CHECK(idx && dout && dq && dk_acc && dv_acc, "ltam_max_bwd_tab: null pointer");
+  k.idx = const_cast<int*>(idx); k.dout = (const char*)dout; k.dq = (char*)dq;
+  for (int j = 0; j < t; ++j) VMG_CHECK(dk_acc[j] && dv_acc[j], "ltam_max_bwd: null accumulator %d", j);
+  if (int rc = table_ltmax(k, keys, vals, dk_acc, dv_acc, t, ws, ws_bytes, (hipStream_t)stream)) return rc;
+  return dtype == VMG_BF16 ? dispatch_ltmax<bf16, LtmaxTabK>(k, true, (hipStream_t)stream) : dispatch_ltmax<float, LtmaxTabK>(k, true, (hipStream_t)stream);
+}

@@ -1629,6 +1629,51 @@ def ltam_attention(q, keys, vals, loc, rpe, decay_v, heads: int, wh: int, ww: in
     return _LTAM.apply(q, loc, rpe, decay_v, (heads, wh, ww, float(scale), banks), *keys, *vals)
 
 
+class _LTAMMax(_Fn):
+    @staticmethod
+    def forward(ctx, q, loc, cfg, *kv):
+        heads, banks = cfg
+        t = len(kv) // 2
+        keys = [x.contiguous() for x in kv[:t]]
+        vals = [x.contiguous() for x in kv[t:]]
+        q = q.contiguous()
+        loc = loc.contiguous()
+        fwd = K.ltam_max_forward if ltam_route(t) == "args" else K.ltam_max_forward_tab
+        out, idx, _ = fwd(q, keys, vals, loc, heads)
+        ctx.cfg = cfg
+        ctx.t = t
+        ctx.save_for_backward(q, loc, idx, *keys, *vals)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        heads, banks = ctx.cfg
+        t = ctx.t
+        q, loc, idx = ctx.saved_tensors[:3]
+        keys = list(ctx.saved_tensors[3:3 + t])
+        vals = list(ctx.saved_tensors[3 + t:])
+        into = []
+        for i, b in enumerate(banks):
+            if b is None or not ctx.needs_input_grad[3 + i]:
+                into.append(None)
+                continue
+            if b.buf is None:
+                b.buf = K.ACC_POOL.take(q.shape, q.device) if q.dtype != torch.float32 else torch.zeros_like(q, dtype=torch.float32)
+            into.append(b.buf)
+        bwd = K.ltam_max_backward if ltam_route(t) == "args" else K.ltam_max_backward_tab
+        dq, dk, dv = bwd(q, keys, vals, loc, idx, dout, heads, dk_into=into[:t], dv_into=into[t:])
+        gkv = [None if into[i] is not None else (g if g.dtype == q.dtype else g.to(q.dtype)) for i, g in enumerate(dk + dv)]
+        return (dq, None, None, *gkv)
+
+
+def ltam_max_attention(q, keys, vals, loc, heads: int):
+    """LTAM_multi_head.forward_max without the output projection (models/trajectory.py:550-670): per pixel and head the value slice of the key-frame
+    whose key is most similar to the query (the first on a tie), weighted by that similarity.  The selection is saved by the forward and is a constant of
+    the backward.  keys / vals that went through grad_bank get their gradients accumulated in place across calls, as in ltam_attention."""
+    banks = tuple(getattr(x, "_vmg_bank", None) for x in list(keys) + list(vals))
+    return _LTAMMax.apply(q, loc, (heads, banks), *keys, *vals)
+
+
 # ---- 3-D shifted-window attention (models/swin_3d.py) --------------------------------------------------
 class _Win3dAttention(_Fn):
     """rWindowAttention.attention for every window / head / time slice (swin_3d.py:167-252) with window partition, roll, padding,

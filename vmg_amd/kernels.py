@@ -1184,6 +1184,101 @@ def _ltam_backward(tab, q, keys, vals, loc, rpe, decay, out, lse, dout, heads, w
     return dq, dk, dv, drpe
 
 
+# ---- hard trajectory attention, traj_mode 'max' (vmg_ltam_max_*) ----------------------------------------
+def _ltam_max_check(nm, q, keys, vals, loc, heads):
+    hip.require_cuda(q, loc, *keys, *vals)
+    if q.dim() != 4 or len(keys) != len(vals):
+        raise HipError(f"{nm}: q (n,h,w,c) and as many keys as vals expected")
+    n, h, w, c = q.shape
+    t = len(keys)
+    ts = [q] + list(keys) + list(vals)
+    if any(x.dtype != q.dtype or tuple(x.shape) != (n, h, w, c) or not x.is_contiguous() for x in ts):
+        raise HipError(f"{nm}: q / keys / vals must be contiguous (n,h,w,c) tensors of one dtype")
+    if loc.dtype != torch.float32 or tuple(loc.shape) != (n, 2 * t, h, w) or not loc.is_contiguous():
+        raise HipError(f"{nm}: loc must be contiguous fp32 (n,2t,h,w), got {tuple(loc.shape)} {loc.dtype}")
+    return n, h, w, c, t
+
+
+def _ltam_max_forward(tab, q, keys, vals, loc, heads):
+    nm = "ltam_max_forward_tab" if tab else "ltam_max_forward"
+    n, h, w, c, t = _ltam_max_check(nm, q, keys, vals, loc, heads)
+    if tab and t < 1:
+        raise HipError("ltam_max_forward_tab: at least one key-frame")
+    out = torch.empty_like(q)
+    idx = torch.empty((n, h, w, heads), dtype=torch.int32, device=q.device)
+    score = torch.empty((n, h, w, heads), dtype=torch.float32, device=q.device)
+    if tab:
+        ws = LTAM_TABLES.get(t, q.device)
+        hip.check(hip.lib().vmg_ltam_max_fwd_tab(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), out.data_ptr(),
+                                                 idx.data_ptr(), score.data_ptr(), n, h, w, c, heads, t, ws.data_ptr(), ws.numel(), hip.stream_ptr()),
+                  "vmg_ltam_max_fwd_tab")
+    else:
+        hip.check(hip.lib().vmg_ltam_max_fwd(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), out.data_ptr(),
+                                             idx.data_ptr(), score.data_ptr(), n, h, w, c, heads, t, hip.stream_ptr()), "vmg_ltam_max_fwd")
+    return out, idx, score
+
+
+def ltam_max_forward(q, keys, vals, loc, heads):
+    """Hard trajectory attention (traj_mode 'max'): out (n,h,w,c), idx (n,h,w,heads) int32 -- per pixel and head the FIRST key-frame of maximal
+    similarity -- and score (n,h,w,heads) fp32, that similarity.  Key-frame pointers in the kernel arguments: at most 32 (vmg_ltam_max_fwd)."""
+    return _ltam_max_forward(False, q, keys, vals, loc, heads)
+
+
+def ltam_max_forward_tab(q, keys, vals, loc, heads):
+    """ltam_max_forward over any number of key-frames: their pointers in a device table (vmg_ltam_max_fwd_tab, workspace LTAM_TABLES).  Same bits."""
+    return _ltam_max_forward(True, q, keys, vals, loc, heads)
+
+
+def _ltam_max_backward(tab, q, keys, vals, loc, idx, dout, heads, dk_into=None, dv_into=None):
+    """dq, dk[j], dv[j] for the selection idx (the forward's; never re-decided).  dk / dv: FP32 sums, dk_into / dv_into as _ltam_backward's."""
+    nm = "ltam_max_backward_tab" if tab else "ltam_max_backward"
+    n, h, w, c, t = _ltam_max_check(nm, q, keys, vals, loc, heads)
+    hip.require_cuda(idx, dout)
+    if tab and t < 1:
+        raise HipError("ltam_max_backward_tab: at least one key-frame")
+    if dout.dtype != q.dtype or tuple(dout.shape) != (n, h, w, c):
+        raise HipError(f"{nm}: dout must have q's shape and dtype, got {tuple(dout.shape)} {dout.dtype}")
+    if idx.dtype != torch.int32 or tuple(idx.shape) != (n, h, w, heads) or not idx.is_contiguous():
+        raise HipError(f"{nm}: idx must be contiguous int32 (n,h,w,heads), got {tuple(idx.shape)} {idx.dtype}")
+    dout = dout.contiguous()
+    dq = torch.empty_like(q)
+    dk = list(dk_into) if dk_into is not None else [None] * t
+    dv = list(dv_into) if dv_into is not None else [None] * t
+    if len(dk) != t or len(dv) != t:
+        raise HipError(f"{nm}: one accumulator (or None) per key-frame expected")
+    for a in dk + dv:
+        if a is not None and (a.shape != q.shape or a.dtype != torch.float32 or not a.is_contiguous() or a.device != q.device):
+            raise HipError(f"{nm}: accumulators must be contiguous fp32 tensors of q's shape")
+    fresh = [i for i, a in enumerate(dk + dv) if a is None]
+    if fresh:  # ONE zero-fill for all new accumulators
+        acc = torch.zeros((len(fresh), n, h, w, c), dtype=torch.float32, device=q.device)
+        for slot, i in enumerate(fresh):
+            if i < t:
+                dk[i] = acc[slot]
+            else:
+                dv[i - t] = acc[slot]
+    if tab:
+        ws = LTAM_TABLES.get(t, q.device)
+        hip.check(hip.lib().vmg_ltam_max_bwd_tab(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), idx.data_ptr(),
+                                                 dout.data_ptr(), dq.data_ptr(), _ptrs(dk), _ptrs(dv), n, h, w, c, heads, t, ws.data_ptr(), ws.numel(),
+                                                 hip.stream_ptr()), "vmg_ltam_max_bwd_tab")
+    else:
+        hip.check(hip.lib().vmg_ltam_max_bwd(hip.dtype_code(q.dtype), q.data_ptr(), _ptrs(keys), _ptrs(vals), loc.data_ptr(), idx.data_ptr(),
+                                             dout.data_ptr(), dq.data_ptr(), _ptrs(dk), _ptrs(dv), n, h, w, c, heads, t, hip.stream_ptr()),
+                  "vmg_ltam_max_bwd")
+    return dq, dk, dv
+
+
+def ltam_max_backward(q, keys, vals, loc, idx, dout, heads, dk_into=None, dv_into=None):
+    """Key-frame pointers in the kernel arguments: at most 32 key-frames (vmg_ltam_max_bwd).  See _ltam_max_backward."""
+    return _ltam_max_backward(False, q, keys, vals, loc, idx, dout, heads, dk_into, dv_into)
+
+
+def ltam_max_backward_tab(q, keys, vals, loc, idx, dout, heads, dk_into=None, dv_into=None):
+    """ltam_max_backward over any number of key-frames (vmg_ltam_max_bwd_tab, workspace LTAM_TABLES): same checks, same dk_into / dv_into semantics."""
+    return _ltam_max_backward(True, q, keys, vals, loc, idx, dout, heads, dk_into, dv_into)
+
+
 OP_CA_FWD, OP_CA_BWD, OP_MIX_FWD, OP_MIX_BWD, OP_GATE_FWD, OP_GATE_BWD, OP_AFFINE2, OP_SCALE, OP_GATE_RES_FWD, OP_GATE_RES_BWD = range(10)
 
 

@@ -371,13 +371,20 @@ class ResidualBlocksWithInputConv(nn.Module):
 
 
 class LTAM_multi_head(nn.Module):
-    """Window trajectory attention (trajectory.py:493-547, 672-795), mode 'wins'."""
+    """Trajectory attention (trajectory.py:493-547): mode 'wins', window attention (:672-795), or mode 'max', hard attention (:550-670) -- which has
+    neither the relative position table nor the decay buffer (its state-dict keys are proj.weight and proj.bias) and whose scale is 1 (:512-515)."""
 
-    def __init__(self, embed_dim, head, if_scale, twins):
+    def __init__(self, embed_dim, head, if_scale, twins, mode="wins"):
         super().__init__()
+        if mode not in ("wins", "max"):
+            raise NotImplementedError(f"LTAM_multi_head: mode 'wins' or 'max', got {mode!r}")
+        self.mode = mode
         self.head = head
-        self.scale = (embed_dim // head) ** -0.5 if if_scale else 1.0
         self.proj = nn.Linear(embed_dim, embed_dim)
+        if mode == "max":
+            self.scale = 1.0
+            return
+        self.scale = (embed_dim // head) ** -0.5 if if_scale else 1.0
         self.win_h, self.win_w = twins
         self.relative_pos_encoding = nn.Parameter(torch.zeros(head, self.win_h * self.win_w, self.win_h * self.win_w))
         nn.init.trunc_normal_(self.relative_pos_encoding, std=.02)
@@ -385,8 +392,11 @@ class LTAM_multi_head(nn.Module):
 
     def forward(self, q, keys, anchor, vals, loc):
         """q, anchor (n,h,w,c); keys, vals: lists of t tensors (n,h,w,c); loc (n,2t,h,w) -> (n,h,w,c)."""
-        att = FH.ltam_attention(q, keys, vals, loc, self.relative_pos_encoding, self.decay_v, self.head, self.win_h, self.win_w,
-                                self.scale)
+        if self.mode == "max":
+            att = FH.ltam_max_attention(q, keys, vals, loc, self.head)
+        else:
+            att = FH.ltam_attention(q, keys, vals, loc, self.relative_pos_encoding, self.decay_v, self.head, self.win_h, self.win_w,
+                                    self.scale)
         return lin(self.proj, att, res=anchor)
 
 
@@ -394,11 +404,11 @@ class Trajectory_multi_head(nn.Module):
     """Bidirectional recurrence (trajectory.py:226-490): warp state by flow, attend to key-frame memory at tracked
     locations, then the residual conv chain; finally fuse [backward, input, forward] with a 1x1 conv."""
 
-    def __init__(self, embed_dim, num_blocks, frame_stride, head, head_scale, r_scaling, twins):
+    def __init__(self, embed_dim, num_blocks, frame_stride, head, head_scale, r_scaling, twins, mode="wins"):
         super().__init__()
         self.embed_dims = embed_dim
         self.keyframe_stride = frame_stride
-        self.LTAM = LTAM_multi_head(embed_dim, head, head_scale, twins)
+        self.LTAM = LTAM_multi_head(embed_dim, head, head_scale, twins, mode)
         self.resblocks = ResidualBlocksWithInputConv(2 * embed_dim, embed_dim, num_blocks, r_scaling)
         self.fusion = nn.Conv2d(3 * embed_dim, embed_dim, 1, 1, 0)
 
@@ -563,7 +573,7 @@ class Mlp_encoder(nn.Module):
 
     def __init__(self, embed_dim, depth, segm, chunk_dim_h, chunk_dim_w, mlp_ratio, n_groups, qkv_bias, drop_path, window_size,
                  n_nonkeyframes, aligned, empty_aligned, traj_r_n, traj_heads, if_smooth, region_range, ffn_type, r_scaling, twins,
-                 traj_scale, m_scaling, if_local_fuse, channel_mixer):
+                 traj_scale, m_scaling, if_local_fuse, channel_mixer, traj_mode="wins"):
         super().__init__()
         self.aligned, self.empty = aligned, empty_aligned
         self.takes_flows, self.keeps_flow_scale = self.flow_use(aligned, empty_aligned)
@@ -580,7 +590,7 @@ class Mlp_encoder(nn.Module):
         if aligned is None:
             self.traj_mixing = nn.Identity() if empty_aligned else DecoderLayer(embed_dim, 2, segm, window_size, mlp_ratio, qkv_bias)
         else:
-            self.traj_mixing = Trajectory_multi_head(embed_dim, traj_r_n, n_nonkeyframes, traj_heads, traj_scale, r_scaling, twins)
+            self.traj_mixing = Trajectory_multi_head(embed_dim, traj_r_n, n_nonkeyframes, traj_heads, traj_scale, r_scaling, twins, traj_mode)
 
     @staticmethod
     def flow_use(aligned, empty_aligned):
@@ -666,8 +676,8 @@ class VMG(nn.Module):
         if not (ltam and retention_decay and non_linear and gating and symm and relu_scale) or relu_scale_norm or if_concat:
             raise NotImplementedError("VMG HIP path: ltam/retention_decay/non_linear/gating/symm/relu_scale must be true, "
                                       "relu_scale_norm/if_concat false (as in all shipped configs)")
-        if symm_act not in ("tanh", nn.Tanh) or traj_mode != "wins" or any(m != "mlps" for m in mixer_type[:len(depths) // 2 + 1]):
-            raise NotImplementedError("VMG HIP path: symm_act='tanh', traj_mode='wins', mixer_type='mlps' only")
+        if symm_act not in ("tanh", nn.Tanh) or traj_mode not in ("wins", "max") or any(m != "mlps" for m in mixer_type[:len(depths) // 2 + 1]):
+            raise NotImplementedError("VMG HIP path: symm_act='tanh', traj_mode 'wins' or 'max', mixer_type='mlps' only")
         if back_RBs != 0 or traj_refine is not None:
             raise NotImplementedError("back_RBs > 0 / traj_refine are not used by any shipped config")
         self.num_layers = len(depths)
@@ -702,7 +712,7 @@ class VMG(nn.Module):
         def stage(dim, depth, heads, ch, cw, dpr, ws, nk, al, rn, th):
             return Mlp_encoder(dim, depth, heads, ch, cw, mlp_ratio, n_groups, qkv_bias, dpr, ws, nk, al, temporal_empty, rn, th,
                                flow_smooth, smooth_region_range, ffn_type, r_scaling, twins, traj_scale, m_scaling, if_local_fuse,
-                               channel_mixer)
+                               channel_mixer, traj_mode)
 
         self.encoder_layers, self.upsample, self.downsample = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         for i in range(self.num_enc_layers):
