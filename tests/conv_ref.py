@@ -1,7 +1,8 @@
-"""Reference of the OPERATION behind vmg_conv_fwd (include/vmg_hip.h) for ks = 3, spelled the slow obvious way in fp64, and the inputs that
-make a comparison with it EXACT: torch and numpy only, nothing of vmg_amd.
+"""Reference of the OPERATION behind vmg_conv_fwd (include/vmg_hip.h) for ks = 3 and ks = 7 (the weight's own size says which; padding
+p = ks // 2, ks * ks taps), spelled the slow obvious way in fp64, and the inputs that make a comparison with it EXACT: torch and numpy only,
+nothing of vmg_amd.
 
-    acc[n,y,x,o] = sum_s sum_{ky,kx} sum_i X_s[n, y+ky-1, x+kx-1, i] * W[o0+o, off_s+i, ky, kx]          (zero outside the image)
+    acc[n,y,x,o] = sum_s sum_{ky,kx} sum_i X_s[n, y+ky-p, x+kx-p, i] * W[o0+o, off_s+i, ky, kx]          (zero outside the image)
     v = acc + bias;  out_pre = bf16(v);  v = act(v);  v *= alpha;  v *= mask(aux, actgrad);  v += res;  out = bf16(v)
 
 The kernels multiply bf16 values exactly into fp32 and add in fp32, each in an order of its own (waves that split K, stages walked in a
@@ -14,7 +15,7 @@ The data gradient has a spelling of its own (a scatter per tap, dgrad_ref): the 
 is not the forward reference with a flipped weight.
 
 ks = 1 (every nn.Linear and 1x1 conv) has references of its own -- linear_ref, dlinear_ref, pixel_shuffle_ref, gelu_ref, gelu_grad_ref --
-that do not go through conv_ref; assert_exact and real_bound take the tap count (taps = 1), epilogue_ref the output dtype."""
+that do not go through conv_ref; assert_exact and real_bound take the tap count (taps = 1; 49 for 7x7), epilogue_ref the output dtype."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -25,13 +26,14 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_GELU = 0, 1, 2, 3  # include/vmg_hip.h VMG_AC
 
 
 def conv_ref(srcs, w, src_off=None, o0=0, on=None, groups=1):
-    """3x3 convolution with zero padding 1 over the virtual concatenation of srcs[s] (N, H, W, C_s), channels-last, in fp64.
-    w (O, I, 3, 3); source s meets the weight's input channels [src_off[s], src_off[s] + C_s) (default: one after the other); the result
+    """3x3 (7x7) convolution with zero padding 1 (3) over the virtual concatenation of srcs[s] (N, H, W, C_s), channels-last, in fp64: a
+    gather per tap.  w (O, I, ks, ks), ks = 3 or 7; source s meets the weight's input channels [src_off[s], src_off[s] + C_s) (default: one after the other); the result
     holds output channels [o0, o0 + on).  groups > 1: w is the weight of a grouped convolution (I channels per group) over the
     concatenated sources -- each group of outputs sees its own I input channels only."""
     N, H, W = srcs[0].shape[:3]
     O = w.shape[0]
     on = O - o0 if on is None else on
+    ks = _ks(w)
     w = w.double()
     if groups > 1:
         assert src_off is None and o0 == 0 and on == O and O % groups == 0
@@ -48,26 +50,34 @@ def conv_ref(srcs, w, src_off=None, o0=0, on=None, groups=1):
     for s, off in zip(srcs, src_off):
         C = s.shape[-1]
         assert tuple(s.shape[:3]) == (N, H, W) and off + C <= w.shape[1]
-        xpad = F.pad(s.double(), (0, 0, 1, 1, 1, 1))
-        for ky in range(3):
-            for kx in range(3):
+        xpad = F.pad(s.double(), (0, 0, ks // 2, ks // 2, ks // 2, ks // 2))
+        for ky in range(ks):
+            for kx in range(ks):
                 acc += torch.einsum("nhwi,oi->nhwo", xpad[:, ky:ky + H, kx:kx + W], w[o0:o0 + on, off:off + C, ky, kx])
     return acc
 
 
+def _ks(w):
+    """The kernel size of a weight (O, I, ks, ks): 3 or 7."""
+    assert w.dim() == 4 and w.shape[2] == w.shape[3] and w.shape[2] in (3, 7), f"weight {tuple(w.shape)}: ks must be 3 or 7"
+    return int(w.shape[2])
+
+
 def dgrad_ref(dy, w, i0=0, inn=None):
-    """Data gradient of the 3x3 convolution y = conv(x, w), w (O, I, 3, 3), as a scatter per tap, in fp64:
-    dx[n, y+ky-1, x+kx-1, i] += dy[n, y, x, o] * w[o, i, ky, kx] -- output pixel (y, x) read input pixel (y+ky-1, x+kx-1) through tap (ky, kx).
+    """Data gradient of the 3x3 (7x7) convolution y = conv(x, w), w (O, I, ks, ks), p = ks // 2, as a scatter per tap, in fp64:
+    dx[n, y+ky-p, x+kx-p, i] += dy[n, y, x, o] * w[o, i, ky, kx] -- output pixel (y, x) read input pixel (y+ky-p, x+kx-p) through tap (ky, kx).
     dy (N, H, W, O); the result holds input channels [i0, i0 + inn)."""
     N, H, W, O = dy.shape
     assert w.shape[0] == O
     inn = w.shape[1] - i0 if inn is None else inn
+    ks = _ks(w)
+    p = ks // 2
     w, dy = w.double(), dy.double()
-    dxp = torch.zeros(N, H + 2, W + 2, inn, dtype=torch.float64)  # dxp[:, 1 + y', 1 + x'] = dx[:, y', x']
-    for ky in range(3):
-        for kx in range(3):
+    dxp = torch.zeros(N, H + 2 * p, W + 2 * p, inn, dtype=torch.float64)  # dxp[:, p + y', p + x'] = dx[:, y', x']
+    for ky in range(ks):
+        for kx in range(ks):
             dxp[:, ky:ky + H, kx:kx + W] += torch.einsum("nhwo,oi->nhwi", dy, w[:, i0:i0 + inn, ky, kx])
-    return dxp[:, 1:H + 1, 1:W + 1].contiguous()
+    return dxp[:, p:H + p, p:W + p].contiguous()
 
 
 def linear_ref(srcs, w, src_off=None, o0=0, on=None):
@@ -183,7 +193,7 @@ def epilogue_ref(acc, bias=None, act=ACT_NONE, slope=0.0, alpha=1.0, aux=None, a
 
 def assert_exact(family, ci_total, bias=True, res=False, scales=(), taps=9):
     """The invariant, checked before anything runs on the GPU.  Operands k * 2^-s of the family: a partial sum is an integer of at most
-    P = kmax^2 * taps * ci_total units of 2^-2s (taps = 9 for 3x3, 1 for ks = 1), the bias adds at most kmax * 2^s of those units.  Every scale (LeakyReLU slope, alpha, the
+    P = kmax^2 * taps * ci_total units of 2^-2s (taps = 9 for 3x3, 49 for 7x7, 1 for ks = 1), the bias adds at most kmax * 2^s of those units.  Every scale (LeakyReLU slope, alpha, the
     slope of mask mode 2) is a power of two 2^-a_j, a_j >= 0: scaling keeps the integer and moves the grid to 2^-(2s+a), a = sum a_j, on
     which the residual is at most kmax * 2^(s+a) units.  Their sum below 2^24 bounds the integer of every intermediate value (conservatively
     for the ones on coarser grids), so each fits fp32's 24-bit significand.  ONE scale may be no power of two if nothing follows it -- no
@@ -203,24 +213,29 @@ def assert_exact(family, ci_total, bias=True, res=False, scales=(), taps=9):
     assert total < 2 ** 24, f"family {family!r} is not exact at {ci_total} input channels (shift {a}): {total} >= 2^24"
 
 
-def one_hot_weight(O, I, t):
-    """Shift probe t (0..8): output channel o has a single 1, at input channel (7 * o + 31 * t) % I and tap (o + t) % 9 -- output channel o is
-    then a shifted copy of that input channel, exact for ANY bf16 input.  Returns (w (O, I, 3, 3) fp32, input channel per o, tap per o)."""
+def one_hot_weight(O, I, t, ks=3):
+    """Shift probe t (0 .. ks * ks - 1): output channel o has a single 1, at input channel (7 * o + 31 * t) % I and tap (o + t) % (ks * ks), the
+    tap (ky, kx) numbered ky * ks + kx -- output channel o is then a shifted copy of that input channel, exact for ANY input.
+    Returns (w (O, I, ks, ks) fp32, input channel per o, tap per o)."""
+    assert ks in (3, 7) and 0 <= t < ks * ks
     o = torch.arange(O)
     i = (7 * o + 31 * t) % I
-    tap = (o + t) % 9
-    w = torch.zeros(O, I, 3, 3)
-    w[o, i, tap // 3, tap % 3] = 1.0
+    tap = (o + t) % (ks * ks)
+    w = torch.zeros(O, I, ks, ks)
+    w[o, i, tap // ks, tap % ks] = 1.0
     return w, i, tap
 
 
-def shifted_copy(x, i, tap):
-    """What a shift probe must give, by indexing alone: out[n, y, x, o] = X[n, y + ky - 1, x + kx - 1, i[o]], zero outside the image."""
+def shifted_copy(x, i, tap, ks=3):
+    """What a shift probe must give, by indexing alone: out[n, y, x, o] = X[n, y + ky - p, x + kx - p, i[o]], p = ks // 2, zero outside the
+    image."""
+    assert ks in (3, 7)
     N, H, W, _ = x.shape
-    xpad = F.pad(x, (0, 0, 1, 1, 1, 1))
+    p = ks // 2
+    xpad = F.pad(x, (0, 0, p, p, p, p))
     out = torch.empty(N, H, W, len(i), dtype=x.dtype)
     for o in range(len(i)):
-        ky, kx = int(tap[o]) // 3, int(tap[o]) % 3
+        ky, kx = int(tap[o]) // ks, int(tap[o]) % ks
         out[..., o] = xpad[:, ky:ky + H, kx:kx + W, int(i[o])]
     return out
 
@@ -246,7 +261,7 @@ def real_bound(v, S, ci_total, taps=9, out_dtype=torch.bfloat16):
     |b| + |res|, e32 = sum_bound(S, ci_total, taps).  The rounding of the computed value to the output type adds u_out of it -- 2^-8 for bf16
     (2^-9 would do for round to nearest; an ulp is allowed), 2^-23 for fp32: |got - v| <= u_out * (|v| + e32) + e32.  ReLU, LeakyReLU, the
     masks and alpha <= 1 do not enlarge it: they are 1-Lipschitz or do not depend on computed values.  taps: products per input channel
-    (9 for 3x3, 1 for ks = 1)."""
+    (9 for 3x3, 49 for 7x7, 1 for ks = 1)."""
     e32 = sum_bound(S, ci_total, taps)
     u_out = 2.0 ** -8 if out_dtype == torch.bfloat16 else 2.0 ** -23
     return u_out * (v.abs() + e32) + e32

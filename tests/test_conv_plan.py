@@ -211,3 +211,118 @@ def test_the_3x3_and_7x7_families_are_reported():
     assert plan[:7] == (KSPLIT, 1, 3, 1, 3, 0, 1) and plan[7:10] == (2 * 2 * 1, 3, 0)
     plan, _ = _plan(_desc(2, 7, 15, (8,), 32, 2, hip.CONV_GENERAL, ks=7, dtype=0))
     assert plan[:7] == (IGEMM, 0, 7, 1, 2, 0, 0) and plan[7:10] == (4, 1, 0)
+
+
+# ---- the table of tests/test_conv_general_kernels_gpu.py: the general 3x3 / 7x7 kernel and the weights-stationary kernel --------------------
+from tests import test_conv_general_kernels_gpu as GG  # noqa: E402
+
+
+def _full_grid(case, ncu):
+    """What the GPU module asks the live plan: the grid of a weights-stationary launch that fills the device."""
+    hip = _hip()
+    N, H, W = GG.WSTAT_FILL
+    plan, err = _plan(_desc(N, H, W, case.src_ch, case.co, case.kernel[1], hip.CONV_WSTAT, ks=3), ncu)
+    assert err is None and plan[0] == WSTAT, f"{case.id}: {plan} {err}"
+    return plan[7]
+
+
+def _general_geom(case, ncu):
+    return case.geom if case.geom is not None else GG.wstat_rows(_full_grid(case, ncu))
+
+
+def _general_desc(case, ncu=NCU):
+    hip = _hip()
+    N, H, W = _general_geom(case, ncu)
+    dt, ks, tiles, mt, route = GG.request(case)
+    e = GG.EPILOGUES[case.epi]
+    lay = GG.layout(case)
+    deep = dict(general=hip.CONV_GENERAL, wstat=hip.CONV_WSTAT)[route]
+    return _desc(N, H, W, case.src_ch, case.co, tiles, deep, dtype=1 if dt == torch.bfloat16 else 0, ks=ks, mt=mt, src_ps=lay.src_ps, out_ps=lay.out_ps,
+                 res=e.get("res", False), aux=bool(e.get("actgrad")), pre=e.get("want_pre", False), act=e.get("act", 0), actgrad=e.get("actgrad", 0),
+                 pixel_shuffle=e.get("pixel_shuffle", False), res_ps=lay.res_ps, aux_ps=lay.aux_ps, src_off=case.src_off if case.i_total else 0)
+
+
+def test_every_general_and_weights_stationary_case_reaches_the_instance_it_names():
+    cases = GG.all_cases()
+    assert len(cases) > 700
+    for case in cases:
+        plan, err = _plan(_general_desc(case))
+        assert err is None, f"{case.id}: {err}"
+        assert plan[:7] == GG.expected_plan(case), f"{case.id}: the plan says {plan}, the case names {GG.expected_plan(case)}"
+        N, H, W = _general_geom(case, NCU)
+        assert plan[9] == 0 and plan[10] <= 160 * 1024
+        if case.kernel[0] == GG.IG:
+            assert (plan[7], plan[8]) == GG.expected_grid(case, (N, H, W)), f"{case.id}: {plan}"
+        else:
+            tiles = N * -(-H // 8) * -(-W // 16)
+            assert plan[7] == min(NCU, 8 * -(-tiles // 8)) and plan[8] == -(-case.co // (16 * case.kernel[1])), f"{case.id}: {plan}"
+            assert case.kernel[2] == (1 if case.src_ch[0] <= 32 else 2) and len(case.src_ch) == 1
+
+
+def test_the_general_table_reaches_all_39_instances_and_every_fallback_is_one():
+    hip = _hip()
+    reached = {c.kernel for c in GG.all_cases()}
+    assert reached == set(GG.INSTANCES) and len(GG.INSTANCES) == 39, set(GG.INSTANCES) ^ reached
+    # every instance is also reached by an EXACT case on a ragged geometry (no pytest.skip / xfail anywhere in the module: nothing to leave out)
+    ragged = {c.kernel for c in GG.exact_cases() if c.geom and (c.geom[1] % 8 or c.geom[2] % 16)}
+    assert ragged == set(GG.INSTANCES), set(GG.INSTANCES) ^ ragged
+    # both epilogue paths of the general kernel meet the chain module's whole table, for 3x3 in both dtypes and both MT, for 7x7 in both dtypes
+    for vector in (True, False):
+        for dt, ks, mt in (("bf16", 3, 1), ("bf16", 3, 2), ("f32", 3, 1), ("bf16", 7, 1), ("f32", 7, 1)):
+            names = {c.epi for c in GG._epilogue_cases() if c.kernel[:4] == (GG.IG, dt, ks, mt) and (c.co % 16 == 0) == vector and c.out_pad == 8}
+            assert names >= set(GG.CHAIN_TABLE), (vector, dt, ks, mt, set(GG.CHAIN_TABLE) - names)
+    full = {c.epi for c in GG._wstat_cases() if c.kernel[0] == GG.WSTAT and c.kernel[3] == 1}
+    simple = {c.epi for c in GG._wstat_cases() if c.kernel[0] == GG.WSTAT and c.kernel[3] == 0}
+    assert full >= set(GG.WSTAT_FULL) and simple >= set(GG.WSTAT_SIMPLE) | {"plain", "bias"} and not (full & simple)
+    # the probe set of every probed channel case meets every tap (9 / 49) in every 16-channel output tile
+    assert GG.probe_taps_missing(GG.all_cases()) == {}
+    assert {c.kernel[:3] for c in GG._probe_cases() if c.kernel[0] == GG.IG} == {(GG.IG, d, k) for d in ("bf16", "f32") for k in (3, 7)}
+    assert {c.kernel[:3] for c in GG._probe_cases() if c.kernel[0] == GG.WSTAT} == {(GG.WSTAT, n, b) for n in (1, 3, 4) for b in (1, 2)}
+    broken = [c for c in GG._probe_cases() if c.kernel[2] == 7][:3]  # (the check can fail: three of four 7x7 probes leave taps out)
+    assert GG.probe_taps_missing(broken) != {}
+    # the declared fallbacks: the hint (or mt = 2) is really asked for, and the general kernel with MT as named really runs
+    fallbacks = [c for c in GG.all_cases() if c.fallback]
+    assert {c.fallback for c in fallbacks} == {"wstat", "mt2"} and len(fallbacks) >= 9
+    for c in fallbacks:
+        d = _general_desc(c)
+        plan, err = _plan(d)
+        assert err is None and plan[0] == IGEMM and plan[5] == 0 and plan[3] == c.kernel[3], f"{c.id}: {plan} {err}"
+        assert (d.deep == hip.CONV_WSTAT) == (c.fallback == "wstat") and (d.mt == 2 and plan[3] == 1) == (c.fallback == "mt2")
+    assert all(c.fallback or GG.request(c)[4] == ("wstat" if c.kernel[0] == GG.WSTAT else "general") for c in GG.all_cases())
+    # a source pixel stride that is no multiple of 8 is no fallback of the hint: 16-byte rows are demanded of every route
+    for deep in (hip.CONV_WSTAT, hip.CONV_GENERAL):
+        plan, err = _plan(_desc(2, 7, 15, (64,), 64, 4, deep, ks=3, src_ps=(68,)))
+        assert plan is None and err == "conv_fwd: source pixel stride must be >= channels and 16-byte aligned"
+    # the geometries the issue names, on one channel case per kernel family
+    for fam in GG.G3:
+        assert {c.geom for c in GG._geometry_cases() if c.kernel[:4] == fam} == set(GG.GEOMS)
+    for fam in GG.G7:
+        assert {c.geom for c in GG._geometry_cases() if c.kernel[:4] == fam} == set(GG.GEOMS7)
+    for nb in (1, 2):
+        assert {c.geom for c in GG._wstat_cases() if c.kernel[0] == GG.WSTAT and c.kernel[2] == nb and c.geom} >= set(GG.WGEOMS)
+    for mt in (1, 2):
+        blocks = lambda g: g[0] * -(-g[1] // (4 * mt)) * -(-g[2] // 16)  # noqa: E731
+        assert blocks((2, 16, 32)) % 8 == 0 and blocks((1, 24, 81)) % 8 != 0 and blocks((1, 24, 81)) > 15  # 160 channels, 3x3: 5 blocks x 3 tap rows
+
+
+@pytest.mark.parametrize("ncu", [256, 64])
+def test_many_tile_weights_stationary_cases_follow_the_grid(ncu):
+    """The rule the GPU module applies to the live grid, at 256 and at 64 compute units: a workgroup walks three tiles, the XCD bands are uneven."""
+    many = [c for c in GG.all_cases() if c.geom is None]
+    assert len(many) == 2 and {c.kernel for c in many} == {(GG.WSTAT, 1, 1, 0), (GG.WSTAT, 1, 1, 1)} and all(c.src_ch == (8,) and c.co == 16 for c in many)
+    for c in many:
+        grid = _full_grid(c, ncu)
+        assert grid == ncu
+        geom = GG.wstat_rows(grid)
+        plan, err = _plan(_general_desc(c, ncu), ncu)
+        assert err is None and plan[:7] == GG.expected_plan(c) and plan[7] == grid, f"{c.id}: {plan} {err}"
+        ntiles = GG.assert_many_tiles(geom, plan[7])
+        walks, bands = GG.wstat_walk(ntiles, grid)
+        assert max(walks) == 3 and min(walks) >= 1 and 2 * grid < ntiles <= 2 * grid + 12
+        assert geom == {256: (1, 821, 75), 64: (1, 205, 75)}[ncu] and ntiles == {256: 515, 64: 130}[ncu]
+        assert bands == {256: [65] * 7 + [60], 64: [17] * 7 + [11]}[ncu]
+    # the rule refuses what it must
+    with pytest.raises(AssertionError):
+        GG.assert_many_tiles((1, 821, 75), 512)   # two tiles per workgroup at most
+    with pytest.raises(AssertionError):
+        GG.assert_many_tiles((1, 8 * 104 - 3, 75), 256)  # 520 tiles: even bands

@@ -328,3 +328,143 @@ def test_permutation_probes_and_the_one_tap_bound():
     assert float(CR.real_bound(v, S, 144, taps=1)) == 2.0 ** -8 * (2 + e) + e
     assert float(CR.real_bound(v, S, 144, taps=1, out_dtype=torch.float32)) == 2.0 ** -23 * (2 + e) + e
     assert float(CR.real_bound(v, S, 144)) == 2.0 ** -8 * (2 + float(CR.sum_bound(S, 144))) + float(CR.sum_bound(S, 144))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# ks = 7, and the table of tests/test_conv_general_kernels_gpu.py
+# ------------------------------------------------------------------------------------------------------------------------------------
+from tests import test_conv_general_kernels_gpu as GG  # noqa: E402
+
+
+def _conv2d7(x, w):
+    return F.conv2d(x.permute(0, 3, 1, 2), w, padding=3).permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 6, 3, 4), (1, 1, 1, 5, 2), (3, 4, 1, 2, 3), (1, 3, 3, 4, 4), (2, 6, 21, 2, 3), (1, 9, 8, 3, 2)])
+def test_conv_ref_7x7_equals_fp64_conv2d(shape):
+    N, H, W, Ci, Co = shape
+    x, w = _rand((N, H, W, Ci), 41), _rand((Co, Ci, 7, 7), 42)
+    _close(CR.conv_ref([x], w), _conv2d7(x, w))
+    with pytest.raises(AssertionError):
+        CR.conv_ref([x], _rand((Co, Ci, 5, 5), 43))  # 3 or 7, nothing else
+    with pytest.raises(AssertionError):
+        CR.conv_ref([x], _rand((Co, Ci, 3, 7), 43))
+
+
+def test_conv_ref_7x7_concat_and_slices_equal_fp64_conv2d():
+    N, H, W = 2, 4, 9
+    a, b, w = _rand((N, H, W, 3), 44), _rand((N, H, W, 5), 45), _rand((6, 8, 7, 7), 46)
+    full = _conv2d7(torch.cat([a, b], -1), w)
+    _close(CR.conv_ref([a, b], w), full)
+    _close(CR.conv_ref([a, b], w, o0=1, on=4), full[..., 1:5])
+    _close(CR.conv_ref([b], w, src_off=[3]), _conv2d7(b, w[:, 3:8].contiguous()))
+    _close(CR.conv_ref([b, a], w, src_off=[3, 0]), full)
+    # a weight that is not symmetric under a flip: the tap order (ky, kx) = (row, column) is torch's
+    w1 = torch.zeros(1, 1, 7, 7, dtype=torch.float64)
+    w1[0, 0, 0, 6] = 1.0  # out[y, x] = in[y - 3, x + 3]
+    x = torch.arange(35, dtype=torch.float64).reshape(1, 5, 7, 1)
+    got = CR.conv_ref([x], w1)
+    assert float(got[0, 3, 2, 0]) == float(x[0, 0, 5, 0]) and float(got[0, 2, 2, 0]) == 0.0 and float(got[0, 4, 4, 0]) == 0.0
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 6, 3, 4), (1, 1, 1, 5, 2), (3, 4, 1, 2, 3), (1, 3, 3, 4, 4), (2, 6, 21, 2, 3)])
+def test_dgrad_ref_7x7_equals_fp64_autograd(shape):
+    N, H, W, Ci, Co = shape
+    x = _rand((N, H, W, Ci), 47).requires_grad_(True)
+    w, dy = _rand((Co, Ci, 7, 7), 48), _rand((N, H, W, Co), 49)
+    gx, = torch.autograd.grad((_conv2d7(x, w) * dy).sum(), [x])
+    got = CR.dgrad_ref(dy, w)
+    assert tuple(got.shape) == (N, H, W, Ci)  # not the weight's other side
+    _close(got, gx)
+    if Ci > 2:
+        _close(CR.dgrad_ref(dy, w, i0=1, inn=2), gx[..., 1:3])
+    # the two spellings are independent: the scatter equals the gather with the transposed, mirrored weight
+    _close(got, CR.conv_ref([dy], w.flip(2, 3).transpose(0, 1).contiguous()))
+
+
+@pytest.mark.parametrize("t", [0, 16, 32, 48, 7])
+def test_shift_probes_7x7_reproduce_shifted_copy_through_conv_ref(t):
+    N, H, W, Ci, Co = 2, 3, 9, 16, 32
+    x = torch.randn(N, H, W, Ci, generator=torch.Generator().manual_seed(t)).bfloat16().float()
+    w, pi, ptap = CR.one_hot_weight(Co, Ci, t, 7)
+    assert tuple(w.shape) == (Co, Ci, 7, 7) and float(w.sum()) == Co and bool((w.reshape(Co, -1).sum(1) == 1).all())
+    assert ptap.tolist() == [(o + t) % 49 for o in range(Co)] and pi.tolist() == [(7 * o + 31 * t) % Ci for o in range(Co)]
+    acc = CR.conv_ref([x], w)
+    want = CR.shifted_copy(x, pi, ptap, 7)
+    assert torch.equal(acc, want.double())
+    # by hand for one element: tap (ky, kx) reads pixel (y + ky - 3, x + kx - 3)
+    o = 5
+    ky, kx = int(ptap[o]) // 7, int(ptap[o]) % 7
+    y, xx = 1, 4
+    yy, xc = y + ky - 3, xx + kx - 3
+    assert float(want[1, y, xx, o]) == (float(x[1, yy, xc, int(pi[o])]) if 0 <= yy < H and 0 <= xc < W else 0.0)
+    out, _ = CR.epilogue_ref(acc)  # asserts that nothing is rounded
+    assert torch.equal(out.float(), acc.float())
+    assert not torch.equal(CR.shifted_copy(x, pi, (ptap + 1) % 49, 7).double(), acc)  # a probe moved by one tap is another tensor
+    # four probes meet every tap in every 16-channel tile; the 3x3 form is unchanged by the new argument
+    taps = [set() for _ in range(Co // 16)]
+    for p in GG.PROBES7:
+        tp = CR.one_hot_weight(Co, Ci, p, 7)[2]
+        for tile in range(Co // 16):
+            taps[tile] |= set(tp[16 * tile:16 * tile + 16].tolist())
+    assert all(s == set(range(49)) for s in taps)
+    w3, i3, t3 = CR.one_hot_weight(Co, Ci, 4)
+    assert tuple(w3.shape) == (Co, Ci, 3, 3) and t3.tolist() == [(o + 4) % 9 for o in range(Co)] and torch.equal(i3, CR.one_hot_weight(Co, Ci, 4, 3)[1])
+
+
+def test_assert_exact_with_49_taps_accepts_every_general_gpu_case_and_no_more():
+    cases = GG.exact_cases()
+    assert len(cases) > 700
+    for c in cases:
+        args = GG.exact_args(c)
+        assert args[5] == (49 if c.ks == 7 else 9)
+        CR.assert_exact(*args[:5], taps=args[5])
+        assert c.fam == ("full" if c.ks == 3 and sum(c.src_ch) <= 28 else "small")  # "full" wherever the taps admit it
+    assert {sum(c.src_ch) for c in cases if c.fam == "full"} == {8, 16, 24}
+    CR.assert_exact("full", 5, bias=True, taps=49)  # 255^2 * 245 + 255 * 2^7 = 15 963 765 < 2^24
+    assert 255 ** 2 * 49 * 5 + 255 * 2 ** 7 == 15963765 < 2 ** 24 < 255 ** 2 * 49 * 6
+    with pytest.raises(AssertionError):
+        CR.assert_exact("full", 6, bias=False, taps=49)
+    with pytest.raises(AssertionError):
+        CR.assert_exact("full", 8, taps=49)  # the narrowest source a kernel takes
+    CR.assert_exact("full", 28, bias=True, res=True, scales=(0.5, 0.25))  # 3x3: 255^2 * 252 + 255 * 2^7 * (1 + 8) < 2^24
+    with pytest.raises(AssertionError):
+        CR.assert_exact("full", 29)
+    CR.assert_exact("small", 64, bias=True, res=True, scales=(0.5, 0.25), taps=49)
+    with pytest.raises(AssertionError):
+        CR.assert_exact("small", 2 ** 13, taps=49)  # 64 * 49 * 8192 > 2^24
+    CR.assert_exact("small", 64, scales=(0.1,), taps=49)
+    with pytest.raises(AssertionError):
+        CR.assert_exact("small", 64, res=True, scales=(0.1,), taps=49)
+
+
+def test_fp32_partial_sums_of_a_7x7_case_in_any_order_reproduce_the_fp64_value():
+    """As for 3x3 above: 49 * 64 products of the "small" family added one by one in fp32 in random orders."""
+    N, H, W, Ci, Co = 1, 3, 8, 64, 3
+    CR.assert_exact("small", Ci, True, True, (0.125,), taps=49)
+    x, w = WR.exact_values((N, H, W, Ci), 51, "small"), WR.exact_values((Co, Ci, 7, 7), 52, "small")
+    x[:], w[0] = 2.0, -2.0  # the worst case in output channel 0: every product -kmax^2 / 16 (the other channels keep their seeded weights)
+    bias, res = WR.exact_values((Co,), 53, "small"), WR.exact_values((N, H, W, Co), 54, "small")
+    acc = CR.conv_ref([x], w)
+    assert float(acc[0, 1, 3, 0]) == -4.0 * Ci * 3 * 7  # three of the seven tap rows lie inside the image
+    want, _ = CR.epilogue_ref(acc, bias, alpha=0.125, res=res)
+    xpad = F.pad(x, (0, 0, 3, 3, 3, 3))
+    cols = torch.stack([xpad[:, ky:ky + H, kx:kx + W] for ky in range(7) for kx in range(7)], -2)  # N, H, W, 49, Ci
+    wt = w.permute(0, 2, 3, 1).reshape(Co, 49, Ci)
+    p32 = (cols[:, :, :, None] * wt[None, None, None]).reshape(N, H, W, Co, 49 * Ci).numpy()
+    rng = np.random.default_rng(5)
+    for _ in range(3):
+        order = rng.permutation(p32.shape[-1])
+        run32 = np.cumsum(p32[..., order], axis=-1, dtype=np.float32)
+        assert np.array_equal(run32.astype(np.float64), np.cumsum(p32[..., order].astype(np.float64), axis=-1))
+        v = (run32[..., -1] + bias.numpy()).astype(np.float32)
+        v = ((v * np.float32(0.125)).astype(np.float32) + res.numpy()).astype(np.float32)
+        assert torch.equal(torch.from_numpy(v).bfloat16(), want)
+
+
+def test_real_bound_with_49_taps():
+    v, S = torch.tensor([2.0], dtype=torch.float64), torch.tensor([3.0], dtype=torch.float64)
+    e = float(CR.sum_bound(S, 32, taps=49))
+    assert e == 2 * (49 * 32 + 4) * 2.0 ** -24 * 3
+    assert float(CR.real_bound(v, S, 32, taps=49)) == 2.0 ** -8 * (2 + e) + e
+    assert float(CR.real_bound(v, S, 32, taps=49, out_dtype=torch.float32)) == 2.0 ** -23 * (2 + e) + e
