@@ -388,6 +388,31 @@ int vmg_group_reduce3(int dtype, const void* a, const void* b0, const void* b1, 
 int vmg_tab_elementwise(int dtype, int op, const void* p0, const void* p1, const void* p2, const float* coef, const float* add, float s,
                         void* o0, void* o1, void* o2, int64_t rows, int64_t R, int C, void* stream);
 
+/* ---- the mixer's output gate as configured (models/function.py:659-663, 796-802; gating / if_symm / symm_act of the YAML), one pass each way.
+ * Tensors are (rows, C) channels-last, C a multiple of the 16-byte vector (4 fp32 / 8 bf16); activations and derivatives in fp32, finite for
+ * every finite input.
+ *   form 0, symmetric:   gate = (a + y) * act(y)       da = d * act(y)                dy = d * (act(y) + (a + y) * act'(y))     a = the mixer's input x
+ *   form 1, asymmetric:  gate = silu(a) * gelu(y)      da = d * gelu(y) * silu'(a)    dy = d * silu(a) * gelu'(y)               a = gating_fc(x); act ignored
+ *   act (form 0): VMG_GATE_TANH tanh(y), 1 - t^2;  VMG_GATE_SIGMOID_SYMM sigmoid(y) - 0.5, s(1 - s);  VMG_GATE_RELU max(y, 0), [y > 0];
+ *                 VMG_GATE_GELU y Phi(y) (erf form), Phi(y) + y phi(y);  VMG_GATE_SILU y s(y), s(1 + y(1 - s))
+ *   vmg_gate_fwd / vmg_gate_bwd          out = gate;  d = dout
+ *   vmg_gate_res_fwd / vmg_gate_res_bwd  out = res + round(gate) * coef[g, c];  d = round(dout * coef[g, c]) -- coef (G, C) fp32, the DropPath / scale
+ *                                        coefficient of the TAB residual (function.py:1212-1214), G groups of rows / G rows; round() is to the tensor
+ *                                        dtype, so the result has the bits of the gate followed by vmg_tab_elementwise op 0 / op 7.  The gradient
+ *                                        w.r.t. res is dout itself.
+ * Non-zero (vmg_last_error) on a null pointer, C not a multiple of the vector width, rows not divisible by G, an unknown form or activation. */
+#define VMG_GATE_TANH 0
+#define VMG_GATE_SIGMOID_SYMM 1
+#define VMG_GATE_RELU 2
+#define VMG_GATE_GELU 3
+#define VMG_GATE_SILU 4
+int vmg_gate_fwd(int dtype, int form, int act, const void* a, const void* y, void* out, int64_t rows, int C, void* stream);
+int vmg_gate_bwd(int dtype, int form, int act, const void* dout, const void* a, const void* y, void* da, void* dy, int64_t rows, int C, void* stream);
+int vmg_gate_res_fwd(int dtype, int form, int act, const void* a, const void* y, const void* res, const float* coef, void* out, int64_t rows, int G,
+                     int C, void* stream);
+int vmg_gate_res_bwd(int dtype, int form, int act, const void* dout, const void* a, const void* y, const float* coef, void* da, void* dy,
+                     int64_t rows, int G, int C, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Flow-guided sampling of the trajectory recurrence (models/trajectory.py:71-116 flow_warp, :329-333, :414-417).
  * flow: (N,H,W,2) fp32 pixel offsets (x then y); coordinates follow flow_warp + F.grid_sample(align_corners=True).

@@ -271,6 +271,136 @@ __global__ __launch_bounds__(256) void tab_ew_kernel(int op, const T* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------------ configurable output gate
+// The gate Enhanced_MorphFCs_decay is configured with (models/function.py:659-663, 796-802; activations models/vmg.py:265-274), a family of its
+// own next to tab_ew_kernel's tanh ops: activation, form (symmetric / asymmetric), residual and direction are template parameters, so every
+// instance is a straight-line body of the same shape -- 16-byte loads and stores, a grid-stride loop, no LDS, no atomics.
+//   symmetric   gate = (x + y) * a(y)          dx = d * a(y)               dy = d * (a(y) + (x + y) * a'(y))
+//   asymmetric  gate = silu(g) * gelu(y)       dg = d * gelu(y) * silu'(g) dy = d * silu(g) * gelu'(y)
+//   RES         out = res + round_T(gate) * coef[g, c];  backward d = round_T(dout * coef[g, c])  (the bits of the two-pass form, as OP_GATE_RES_*)
+// a and a' are evaluated in fp32 and are finite for every finite argument (an overflowing expf ends in a sigmoid of 0 or 1).
+enum { GA_TANH = 0, GA_SIGMOID_SYMM = 1, GA_RELU = 2, GA_GELU = 3, GA_SILU = 4, GA_COUNT = 5 };
+
+template <int ACT>
+__device__ __forceinline__ void gate_act(float y, float& a, float& da) {
+  if (ACT == GA_TANH) {
+    const float t = tanhf(y);
+    a = t;
+    da = 1.f - t * t;
+  } else if (ACT == GA_SIGMOID_SYMM) {  // sigmoid(y) - 0.5 = tanh(y / 2) / 2 (no cancellation near 0);  sigma (1 - sigma) = (1 - tanh(y / 2)^2) / 4
+    const float t = tanhf(0.5f * y);
+    a = 0.5f * t;
+    da = 0.25f * (1.f - t * t);
+  } else if (ACT == GA_RELU) {
+    a = fmaxf(y, 0.f);
+    da = y > 0.f ? 1.f : 0.f;
+  } else if (ACT == GA_GELU) {  // (se_act / se_dact's expressions)
+    const float phi = 0.5f * (1.f + erff(y * 0.7071067811865476f));
+    a = y * phi;
+    da = phi + y * expf(-0.5f * y * y) * 0.3989422804014327f;
+  } else {  // GA_SILU
+    const float sg = 1.f / (1.f + expf(-y));
+    a = y * sg;
+    da = sg * (1.f + y * (1.f - sg));
+  }
+}
+
+// forward: p0 = x (symmetric) or g = gating_fc(x) (asymmetric), p1 = y, p2 = res (RES);  o0 = the gate, or res + gate * coef
+// backward: p0 = dout, p1 = x or g, p2 = y;  o0 = dx or dg, o1 = dy
+template <typename T, int ACT, bool ASYM, bool RES, bool BWD>
+__global__ __launch_bounds__(256) void gate_kernel(const T* __restrict__ p0, const T* __restrict__ p1, const T* __restrict__ p2,
+                                                   const float* __restrict__ coef, T* __restrict__ o0, T* __restrict__ o1, long long rows,
+                                                   long long R, int C) {
+  constexpr int VN = V16<T>::N;
+  const int nvec = C / VN;
+  const long long total = rows * nvec;
+  const bool small = total < (1LL << 31);  // (uniform: the usual case divides in 32 bits)
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long off = i * VN;  // = row * C + v * VN: the tensors are dense, only the coefficient needs (group, channel)
+    long long gc = 0;
+    if (RES) {
+      if (small) {
+        const unsigned row = (unsigned)i / (unsigned)nvec, v = (unsigned)i - row * (unsigned)nvec;
+        gc = (long long)(row / (unsigned)R) * C + v * VN;
+      } else {
+        const long long row = i / nvec;
+        gc = (row / R) * C + (i - row * nvec) * VN;
+      }
+    }
+    const V16<T> a0 = *reinterpret_cast<const V16<T>*>(p0 + off);
+    const V16<T> a1 = *reinterpret_cast<const V16<T>*>(p1 + off);
+    V16<T> a2, r0, r1;
+    if (BWD || RES) a2 = *reinterpret_cast<const V16<T>*>(p2 + off);
+    if (!BWD) {
+#pragma unroll
+      for (int e = 0; e < VN; ++e) {
+        const float xv = to_f32(a0.v[e]), yv = to_f32(a1.v[e]);
+        float a, da, gate;
+        if (ASYM) {
+          float sx, dsx;
+          gate_act<GA_SILU>(xv, sx, dsx);
+          gate_act<GA_GELU>(yv, a, da);
+          gate = sx * a;
+        } else {
+          gate_act<ACT>(yv, a, da);
+          gate = (xv + yv) * a;
+        }
+        if (RES) r0.v[e] = from_f32<T>(to_f32(from_f32<T>(gate)) * coef[gc + e] + to_f32(a2.v[e]));
+        else r0.v[e] = from_f32<T>(gate);
+      }
+      *reinterpret_cast<V16<T>*>(o0 + off) = r0;
+    } else {
+#pragma unroll
+      for (int e = 0; e < VN; ++e) {
+        const float d = RES ? to_f32(from_f32<T>(to_f32(a0.v[e]) * coef[gc + e])) : to_f32(a0.v[e]);
+        const float xv = to_f32(a1.v[e]), yv = to_f32(a2.v[e]);
+        float a, da;
+        if (ASYM) {
+          float sx, dsx;
+          gate_act<GA_SILU>(xv, sx, dsx);
+          gate_act<GA_GELU>(yv, a, da);
+          r0.v[e] = from_f32<T>(d * a * dsx);
+          r1.v[e] = from_f32<T>(d * sx * da);
+        } else {
+          gate_act<ACT>(yv, a, da);
+          r0.v[e] = from_f32<T>(d * a);
+          r1.v[e] = from_f32<T>(d * (a + (xv + yv) * da));
+        }
+      }
+      *reinterpret_cast<V16<T>*>(o0 + off) = r0;
+      *reinterpret_cast<V16<T>*>(o1 + off) = r1;
+    }
+  }
+}
+
+template <typename T, int ACT, bool ASYM>
+void gate_launch_form(bool res, bool bwd, int blocks, hipStream_t st, const void* p0, const void* p1, const void* p2, const float* coef, void* o0,
+                      void* o1, long long rows, long long R, int C) {
+  const T *q0 = (const T*)p0, *q1 = (const T*)p1, *q2 = (const T*)p2;
+  if (!bwd && !res) hipLaunchKernelGGL((gate_kernel<T, ACT, ASYM, false, false>), dim3(blocks), dim3(256), 0, st, q0, q1, q2, coef, (T*)o0, (T*)o1, rows, R, C);
+  else if (!bwd) hipLaunchKernelGGL((gate_kernel<T, ACT, ASYM, true, false>), dim3(blocks), dim3(256), 0, st, q0, q1, q2, coef, (T*)o0, (T*)o1, rows, R, C);
+  else if (!res) hipLaunchKernelGGL((gate_kernel<T, ACT, ASYM, false, true>), dim3(blocks), dim3(256), 0, st, q0, q1, q2, coef, (T*)o0, (T*)o1, rows, R, C);
+  else hipLaunchKernelGGL((gate_kernel<T, ACT, ASYM, true, true>), dim3(blocks), dim3(256), 0, st, q0, q1, q2, coef, (T*)o0, (T*)o1, rows, R, C);
+}
+
+template <typename T>
+void gate_launch(int form, int act, bool res, bool bwd, int blocks, hipStream_t st, const void* p0, const void* p1, const void* p2,
+                 const float* coef, void* o0, void* o1, long long rows, long long R, int C) {
+#define VMG_GATE_CASE(A) case A: gate_launch_form<T, A, false>(res, bwd, blocks, st, p0, p1, p2, coef, o0, o1, rows, R, C); break;
+  if (form == 1) {
+    gate_launch_form<T, GA_GELU, true>(res, bwd, blocks, st, p0, p1, p2, coef, o0, o1, rows, R, C);
+    return;
+  }
+  switch (act) {
+    VMG_GATE_CASE(GA_TANH)
+    VMG_GATE_CASE(GA_SIGMOID_SYMM)
+    VMG_GATE_CASE(GA_RELU)
+    VMG_GATE_CASE(GA_GELU)
+    VMG_GATE_CASE(GA_SILU)
+  }
+#undef VMG_GATE_CASE
+}
+
 // ------------------------------------------------------------------------------------------------ f x f max pooling
 // The multi-scale skip of VMG (models/vmg.py:388-400): adaptive_max_pool2d to (H/4, W/4) = non-overlapping 4 x 4 windows when the
 // size divides.  Forward keeps the winner's position inside its window (first maximum in row-major order, as ATen does);
@@ -589,4 +719,43 @@ extern "C" int vmg_tab_elementwise(int dtype, int op, const void* p0, const void
                        s, (float*)o0, (float*)o1, (float*)o2, (long long)rows, (long long)R, C);
   VMG_LAUNCH_CHECK();
   return 0;
+}
+
+// The gate family (gate_kernel): shared argument checks and launch.  form 0 symmetric (act one of VMG_GATE_*), form 1 asymmetric (act ignored:
+// silu(g) * gelu(y)).  coef != nullptr selects the residual instances.
+static int gate_dispatch(const char* who, int dtype, int form, int act, bool res, bool bwd, const void* p0, const void* p1, const void* p2,
+                         const float* coef, void* o0, void* o1, int64_t rows, int G, int C, void* stream) {
+  VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "%s: bad dtype", who);
+  VMG_CHECK(form == 0 || form == 1, "%s: form is 0 (symmetric) or 1 (asymmetric)", who);
+  VMG_CHECK(form == 1 || (act >= 0 && act < GA_COUNT), "%s: unknown activation %d (tanh 0, sigmoid_symm 1, relu 2, gelu 3, silu 4)", who, act);
+  VMG_CHECK(p0 && p1 && o0 && (p2 || !(res || bwd)) && (o1 || !bwd) && (coef || !res), "%s: null pointer", who);
+  const int vn = dtype == VMG_BF16 ? 8 : 4;
+  VMG_CHECK(C > 0 && C % vn == 0, "%s: C must be a multiple of %d", who, vn);
+  VMG_CHECK(rows > 0 && G > 0 && rows % G == 0, "%s: %lld rows do not split into G = %d groups", who, (long long)rows, G);
+  VMG_CHECK((((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)o0 | (uintptr_t)o1) % 16) == 0, "%s: pointers must be 16-byte aligned", who);
+  const long long total = rows * (C / vn);
+  const int blocks = (int)(cdiv64(total, 256) > 8192 ? 8192 : cdiv64(total, 256));
+  if (dtype == VMG_BF16) gate_launch<bf16>(form, act, res, bwd, blocks, (hipStream_t)stream, p0, p1, p2, coef, o0, o1, rows, rows / G, C);
+  else gate_launch<float>(form, act, res, bwd, blocks, (hipStream_t)stream, p0, p1, p2, coef, o0, o1, rows, rows / G, C);
+  VMG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vmg_gate_fwd(int dtype, int form, int act, const void* a, const void* y, void* out, int64_t rows, int C, void* stream) {
+  return gate_dispatch("gate_fwd", dtype, form, act, false, false, a, y, nullptr, nullptr, out, nullptr, rows, 1, C, stream);
+}
+
+extern "C" int vmg_gate_bwd(int dtype, int form, int act, const void* dout, const void* a, const void* y, void* da, void* dy, int64_t rows, int C,
+                            void* stream) {
+  return gate_dispatch("gate_bwd", dtype, form, act, false, true, dout, a, y, nullptr, da, dy, rows, 1, C, stream);
+}
+
+extern "C" int vmg_gate_res_fwd(int dtype, int form, int act, const void* a, const void* y, const void* res, const float* coef, void* out,
+                                int64_t rows, int G, int C, void* stream) {
+  return gate_dispatch("gate_res_fwd", dtype, form, act, true, false, a, y, res, coef, out, nullptr, rows, G, C, stream);
+}
+
+extern "C" int vmg_gate_res_bwd(int dtype, int form, int act, const void* dout, const void* a, const void* y, const float* coef, void* da, void* dy,
+                                int64_t rows, int G, int C, void* stream) {
+  return gate_dispatch("gate_res_bwd", dtype, form, act, true, true, dout, a, y, coef, da, dy, rows, G, C, stream);
 }

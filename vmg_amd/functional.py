@@ -1247,8 +1247,9 @@ class _GateResidual(_Fn):
 _ONES = {}
 
 
-def gate_residual(x: torch.Tensor, y: torch.Tensor, res: torch.Tensor, p: float, training: bool, scale: float = 1.0) -> torch.Tensor:
-    """res + DropPath_p((x + y) * tanh(y)) * scale (timm DropPath semantics, see residual_drop_path) as one kernel."""
+def _gate_coef(y: torch.Tensor, p: float, training: bool, scale: float) -> torch.Tensor:
+    """The (B, C) fp32 coefficient of `res + DropPath_p(gate) * scale` for a gate shaped like y: from the DropPath plan when it is in step (DROP.take),
+    a per-call draw otherwise, a cached constant when nothing is dropped."""
     B, C = y.shape[0], y.shape[-1]
     if p > 0.0 and training:
         keep = 1.0 - p
@@ -1263,7 +1264,69 @@ def gate_residual(x: torch.Tensor, y: torch.Tensor, res: torch.Tensor, p: float,
         g = _ONES.get(key)
         if g is None:
             g = _ONES[key] = torch.full((B, C), float(scale), dtype=torch.float32, device=y.device)
-    return _GateResidual.apply(x, y, res, g)
+    return g
+
+
+def gate_residual(x: torch.Tensor, y: torch.Tensor, res: torch.Tensor, p: float, training: bool, scale: float = 1.0) -> torch.Tensor:
+    """res + DropPath_p((x + y) * tanh(y)) * scale (timm DropPath semantics, see residual_drop_path) as one kernel."""
+    return _GateResidual.apply(x, y, res, _gate_coef(y, p, training, scale))
+
+
+class _Gate(_Fn):
+    """The mixer's output gate as the reference configures it (models/function.py:659-663, 796-802), on the gate kernel family (kernels.gate_forward):
+    symmetric (a + y) * act(y) with a = the mixer's input, or asymmetric silu(a) * gelu(y) with a = gating_fc(x)."""
+
+    @staticmethod
+    def forward(ctx, a, y, act, asym):
+        a, y = a.contiguous(), y.contiguous()
+        ctx.act, ctx.asym = act, asym
+        ctx.save_for_backward(a, y)
+        return K.gate_forward(a, y, act, asym)
+
+    @staticmethod
+    def backward(ctx, d):
+        a, y = ctx.saved_tensors
+        da, dy = K.gate_backward(d.contiguous(), a, y, ctx.act, ctx.asym)
+        return da, dy, None, None
+
+
+class _GateRes(_Fn):
+    """res + gate * g with g the (B, C) fp32 DropPath / scale coefficient: _Gate and the TAB residual in one pass each way, with the bits of
+    residual_drop_path(res, gate) -- what _GateResidual is to the tanh gate."""
+
+    @staticmethod
+    def forward(ctx, a, y, res, g, act, asym):
+        a, y, res = a.contiguous(), y.contiguous(), res.contiguous()
+        ctx.act, ctx.asym = act, asym
+        ctx.save_for_backward(a, y, g)
+        return K.gate_forward(a, y, act, asym, res=res, coef=g, G=g.shape[0])
+
+    @staticmethod
+    def backward(ctx, d):
+        a, y, g = ctx.saved_tensors
+        d = d.contiguous()
+        da, dy = K.gate_backward(d, a, y, ctx.act, ctx.asym, coef=g, G=g.shape[0])
+        return da, dy, d, None, None, None
+
+
+def symm_gate(x: torch.Tensor, y: torch.Tensor, act: str) -> torch.Tensor:
+    """(x + y) * act(y), act one of 'tanh', 'sigmoid' (sigmoid(y) - 0.5), 'relu', 'gelu', 'swish' (models/vmg.py:265-274)."""
+    return _Gate.apply(x, y, act, False)
+
+
+def symm_gate_residual(x: torch.Tensor, y: torch.Tensor, res: torch.Tensor, p: float, training: bool, scale: float = 1.0, act: str = "tanh") -> torch.Tensor:
+    """res + DropPath_p(symm_gate(x, y, act)) * scale as one kernel (gate_residual for any activation)."""
+    return _GateRes.apply(x, y, res, _gate_coef(y, p, training, scale), act, False)
+
+
+def asym_gate(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """silu(g) * gelu(y), g = gating_fc(x) (models/function.py:797-799)."""
+    return _Gate.apply(g, y, "gelu", True)
+
+
+def asym_gate_residual(g: torch.Tensor, y: torch.Tensor, res: torch.Tensor, p: float, training: bool, scale: float = 1.0) -> torch.Tensor:
+    """res + DropPath_p(asym_gate(g, y)) * scale as one kernel."""
+    return _GateRes.apply(g, y, res, _gate_coef(y, p, training, scale), "gelu", True)
 
 
 class _MaxPool(_Fn):

@@ -1346,6 +1346,51 @@ def tab_elementwise(op: int, p0, p1=None, p2=None, coef=None, add=None, s: float
     return outs[0] if nout == 1 else outs
 
 
+def _gate_args(who, act, tensors, coef, G):
+    """Shared checks of the gate family: returns (activation code, rows, C)."""
+    hip.require_cuda(*tensors, coef)
+    p0 = tensors[0]
+    if act not in hip.GATE_ACTS:
+        raise HipError(f"{who}: activation {act!r} is not one of {sorted(hip.GATE_ACTS)}")
+    if p0.dtype not in (torch.float32, torch.bfloat16) or any(not t.is_contiguous() or t.shape != p0.shape or t.dtype != p0.dtype for t in tensors):
+        raise HipError(f"{who}: contiguous fp32 / bf16 operands of one shape and dtype expected")
+    C = p0.shape[-1]
+    rows = p0.numel() // C
+    if coef is not None and (G <= 0 or rows % G or coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() != G * C):
+        raise HipError(f"{who}: coef must be contiguous fp32 of G * C = {G * C} elements, G = {G} dividing the {rows} rows")
+    return hip.GATE_ACTS[act], rows, C
+
+
+def gate_forward(a: torch.Tensor, y: torch.Tensor, act: str = "tanh", asym: bool = False, res: Optional[torch.Tensor] = None,
+                 coef: Optional[torch.Tensor] = None, G: int = 1) -> torch.Tensor:
+    """(a + y) * act(y), or silu(a) * gelu(y) with asym (vmg_gate_fwd); with res and coef (G, C) fp32: res + gate * coef (vmg_gate_res_fwd)."""
+    if (res is None) != (coef is None):
+        raise HipError("gate_forward: res and coef come together")
+    code, rows, C = _gate_args("gate_forward", act, [a, y] + ([res] if res is not None else []), coef, G)
+    out = torch.empty_like(a)
+    if res is None:
+        hip.check(hip.lib().vmg_gate_fwd(hip.dtype_code(a.dtype), int(asym), code, a.data_ptr(), y.data_ptr(), out.data_ptr(), rows, C,
+                                         hip.stream_ptr()), "vmg_gate_fwd")
+    else:
+        hip.check(hip.lib().vmg_gate_res_fwd(hip.dtype_code(a.dtype), int(asym), code, a.data_ptr(), y.data_ptr(), res.data_ptr(), coef.data_ptr(),
+                                             out.data_ptr(), rows, G, C, hip.stream_ptr()), "vmg_gate_res_fwd")
+    return out
+
+
+def gate_backward(d: torch.Tensor, a: torch.Tensor, y: torch.Tensor, act: str = "tanh", asym: bool = False, coef: Optional[torch.Tensor] = None,
+                  G: int = 1):
+    """(da, dy) of gate_forward for the output gradient d (vmg_gate_bwd); with coef the gradient is d * coef first (vmg_gate_res_bwd)."""
+    code, rows, C = _gate_args("gate_backward", act, [d, a, y], coef, G)
+    da, dy = torch.empty_like(a), torch.empty_like(a)
+    if coef is None:
+        hip.check(hip.lib().vmg_gate_bwd(hip.dtype_code(a.dtype), int(asym), code, d.data_ptr(), a.data_ptr(), y.data_ptr(), da.data_ptr(),
+                                         dy.data_ptr(), rows, C, hip.stream_ptr()), "vmg_gate_bwd")
+    else:
+        hip.check(hip.lib().vmg_gate_res_bwd(hip.dtype_code(a.dtype), int(asym), code, d.data_ptr(), a.data_ptr(), y.data_ptr(), coef.data_ptr(),
+                                             da.data_ptr(), dy.data_ptr(), rows, G, C, hip.stream_ptr()), "vmg_gate_res_bwd")
+    return da, dy
+
+
 def se_mlp_forward(m: torch.Tensor, w1: torch.Tensor, b1, w2: torch.Tensor, b2, act1: int, mode: int):
     """Squeeze-excite MLP on pooled rows m (G, C) fp32: returns (pre (G, Hd), out (G, Co)); mode 0 sigmoid, mode 1 softmax over triples."""
     hip.require_cuda(m, w1, w2)

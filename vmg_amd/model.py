@@ -240,13 +240,40 @@ class Mlp_cnn(nn.Module):
         return lin(self.fc2, h, res=res, fuse_src_act=True).reshape(B, T, H, W, C)
 
 
-class Enhanced_MorphFCs_decay(nn.Module):
-    """Token mixer: H-, W- and channel-branch, softmax re-weighting, projection, tanh gate
-    (models/function.py:596-805).  STATEFUL like the reference: mlp_h/mlp_w weights are multiplied by
-    gamma_h/gamma_w in place on every forward call (SURVEY trap T1)."""
+class sigmoid_symm(nn.Module):
+    """sigmoid(x) - 0.5: the reference's symmetric sigmoid (models/function.py:18-27), parameter-free."""
 
-    def __init__(self, dim, chunk_h=8, chunk_w=8, qkv_bias=False, channel_mixer="rcab"):
+    def forward(self, x):
+        return torch.sigmoid(x) - 0.5
+
+
+SYMM_ACTS = {"tanh": nn.Tanh, "sigmoid": sigmoid_symm, "relu": nn.ReLU, "gelu": nn.GELU, "swish": nn.SiLU}  # models/vmg.py:265-274
+
+
+def symm_act_name(symm_act) -> str:
+    """The config name of a symmetric-gate activation given as that name or as a module class (the reference's VMG hands Enhanced_MorphFCs_decay
+    classes; its own sigmoid_symm is recognised by name).  ValueError for anything else."""
+    if isinstance(symm_act, str) and symm_act in SYMM_ACTS:
+        return symm_act
+    if isinstance(symm_act, type):
+        for name, cls in SYMM_ACTS.items():
+            if symm_act is cls or (name == "sigmoid" and symm_act.__name__ == "sigmoid_symm"):
+                return name
+    raise ValueError(f"symm_act {symm_act!r}: one of 'tanh', 'sigmoid', 'relu', 'gelu', 'swish' (or nn.Tanh, sigmoid_symm, nn.ReLU, nn.GELU, nn.SiLU)")
+
+
+class Enhanced_MorphFCs_decay(nn.Module):
+    """Token mixer: H-, W- and channel-branch, softmax re-weighting, projection, output gate
+    (models/function.py:596-805).  STATEFUL like the reference: mlp_h/mlp_w weights are multiplied by
+    gamma_h/gamma_w in place on every forward call (SURVEY trap T1).
+
+    The gate (function.py:659-663, 796-802): gating and symm, (x + y) * act(y) with act = symm_act; gating and not symm,
+    silu(gating_fc(x)) * gelu(y) with gating_fc a Linear(dim, dim); not gating, y itself.  x is the mixer's input, y the projection's output."""
+
+    def __init__(self, dim, chunk_h=8, chunk_w=8, qkv_bias=False, channel_mixer="rcab", gating=True, symm=True, symm_act="tanh"):
         super().__init__()
+        self.gating, self.symm = bool(gating), bool(symm)
+        self.symm_act = symm_act_name(symm_act)
         self.chunk_h, self.chunk_w = chunk_h, chunk_w
         self.Ch = int(np.ceil(dim / chunk_h)) * chunk_h
         self.Cw = int(np.ceil(dim / chunk_w)) * chunk_w
@@ -262,14 +289,22 @@ class Enhanced_MorphFCs_decay(nn.Module):
         self.proj = nn.Linear(dim, dim)
         self.register_buffer("gamma_h", decay_gamma(chunk_h, self.Ch))
         self.register_buffer("gamma_w", decay_gamma(chunk_w, self.Cw))
+        # gating_fc as the reference registers it (function.py:659-663), the last child -- the state-dict key order is the reference's: the
+        # asymmetric gate's Linear (the only form with parameters), or the symmetric gate's parameter-free activation module.  The tanh
+        # configuration keeps the module tree it always had here (no child for the activation: the tanh ops of tab_elementwise are its gate)
+        if self.gating and not self.symm:
+            self.gating_fc = nn.Linear(dim, dim)
+        elif self.gating and self.symm_act != "tanh":
+            self.gating_fc = SYMM_ACTS[self.symm_act]()
+        self.n_handles = self.N_HANDLES if self.gating else self.N_HANDLES - 1
 
-    N_HANDLES = 5  # consumers of the mixer's input: H branch, W branch, channel branch (RCAB: conv + residual), tanh gate
+    N_HANDLES = 5  # consumers of the mixer's input: H branch, W branch, channel branch (RCAB: conv + residual), the gate (none with gating=False: n_handles)
 
     def forward(self, x, residual=None):
-        """x: the normalised features (B,T,H,W,C), or a list of N_HANDLES autograd handles of them (functional.layer_norm_fan).
+        """x: the normalised features (B,T,H,W,C), or a list of n_handles autograd handles of them (functional.layer_norm_fan).
         residual = (res, drop_prob, training, scale): return res + DropPath(mixer(x)) * scale instead of mixer(x) -- the TAB residual taken
-        inside the gate's pass (functional.gate_residual)."""
-        xs = list(x) if isinstance(x, (list, tuple)) else [x] * self.N_HANDLES
+        inside the gate's pass (functional.gate_residual / symm_gate_residual / asym_gate_residual)."""
+        xs = list(x) if isinstance(x, (list, tuple)) else [x] * self.n_handles
         x = xs[0]
         B, T, H, W, C = x.shape
         if getattr(self, "_t1_done", False):  # (VMG.forward has applied this call's decay for all mixers at once, FH.decay_weights_and_repack)
@@ -288,6 +323,13 @@ class Enhanced_MorphFCs_decay(nn.Module):
         rw = self.reweight
         y = FH.reweight_mix(h, w, c, rw.fc1.weight, rw.fc1.bias, rw.fc2.weight, rw.fc2.bias)
         y = lin(self.proj, y)
+        if not self.gating:
+            return y if residual is None else FH.residual_drop_path(residual[0], y, *residual[1:])
+        if not self.symm:
+            g = lin(self.gating_fc, xs[4])
+            return FH.asym_gate(g, y) if residual is None else FH.asym_gate_residual(g, y, *residual)
+        if self.symm_act != "tanh":
+            return FH.symm_gate(xs[4], y, self.symm_act) if residual is None else FH.symm_gate_residual(xs[4], y, *residual, act=self.symm_act)
         if residual is not None:
             return FH.gate_residual(xs[4], y, *residual)
         return FH.tanh_gate(xs[4], y)
@@ -312,11 +354,12 @@ def decay_gamma(chunk: int, ch_total: int) -> torch.Tensor:
 class TAB(nn.Module):
     """x += DP(spatial(LN2(x))) * s; x += DP(ffn(LN3(x))) * s (models/function.py:1139-1217)."""
 
-    def __init__(self, embed_dim, chunk_h, chunk_w, mlp_ratio, n_groups, qkv_bias, drop_path, ffn, mixer_scaling, channel_mixer):
+    def __init__(self, embed_dim, chunk_h, chunk_w, mlp_ratio, n_groups, qkv_bias, drop_path, ffn, mixer_scaling, channel_mixer, gating=True,
+                 symm=True, symm_act="tanh"):
         super().__init__()
         self.spatial_scale = mixer_scaling
         self.norm2 = nn.LayerNorm(embed_dim)
-        self.spatial_mixing = Enhanced_MorphFCs_decay(embed_dim, chunk_h, chunk_w, qkv_bias, channel_mixer)
+        self.spatial_mixing = Enhanced_MorphFCs_decay(embed_dim, chunk_h, chunk_w, qkv_bias, channel_mixer, gating, symm, symm_act)
         self.norm3 = nn.LayerNorm(embed_dim)
         if ffn == "vanilla":
             self.channel_mixing = Mlp(embed_dim, int(embed_dim * mlp_ratio))
@@ -330,10 +373,10 @@ class TAB(nn.Module):
         s = self.spatial_scale
         dp = self.drop_prob > 0.0 and self.training
         # x feeds the norm AND the residual: layer_norm_skip hands x back so that both gradients meet in the LayerNorm backward kernel
-        # ... and the mixer reads the normalised tensor five times: layer_norm_fan hands out one autograd handle per consumer, so that ALL their
+        # ... and the mixer reads the normalised tensor five times (four without a gate): layer_norm_fan hands out one autograd handle per consumer, so that ALL their
         # gradients (and the skip gradient) are summed inside the one LayerNorm backward kernel
         if torch.is_grad_enabled() and x.requires_grad:
-            n2, xs = FH.layer_norm_fan(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, Enhanced_MorphFCs_decay.N_HANDLES)
+            n2, xs = FH.layer_norm_fan(x, self.norm2.weight, self.norm2.bias, self.norm2.eps, self.spatial_mixing.n_handles)
         else:
             n2, xs = FH.layer_norm_skip(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)
         x = self.spatial_mixing(n2, residual=(xs, self.drop_prob, self.training, s))  # gate, DropPath mask, scale and residual add: one pass
@@ -573,7 +616,7 @@ class Mlp_encoder(nn.Module):
 
     def __init__(self, embed_dim, depth, segm, chunk_dim_h, chunk_dim_w, mlp_ratio, n_groups, qkv_bias, drop_path, window_size,
                  n_nonkeyframes, aligned, empty_aligned, traj_r_n, traj_heads, if_smooth, region_range, ffn_type, r_scaling, twins,
-                 traj_scale, m_scaling, if_local_fuse, channel_mixer, traj_mode="wins"):
+                 traj_scale, m_scaling, if_local_fuse, channel_mixer, traj_mode="wins", gating=True, symm=True, symm_act="tanh"):
         super().__init__()
         self.aligned, self.empty = aligned, empty_aligned
         self.takes_flows, self.keeps_flow_scale = self.flow_use(aligned, empty_aligned)
@@ -584,7 +627,7 @@ class Mlp_encoder(nn.Module):
             self.local_cnn = nn.Conv2d(embed_dim, embed_dim, 3, 1, 1)
         self.mlp_blocks = nn.ModuleList([TAB(embed_dim, chunk_dim_h, chunk_dim_w, mlp_ratio, n_groups, qkv_bias,
                                              drop_path[i] if isinstance(drop_path, list) else drop_path, ffn_type, m_scaling,
-                                             channel_mixer) for i in range(depth)])
+                                             channel_mixer, gating, symm, symm_act) for i in range(depth)])
         if aligned:
             raise NotImplementedError("temporal_type=True (DCN alignment) is not configured by any shipped config")
         if aligned is None:
@@ -673,11 +716,12 @@ class VMG(nn.Module):
                  m_scaling=1., if_local_fuse=False, channel_mixer='vanilla', compute_dtype=torch.float32, recompute_chains=False, fp8_chains=False):
         super().__init__()
         # --- options the hand-written path implements (every self-consistent shipped config)
-        if not (ltam and retention_decay and non_linear and gating and symm and relu_scale) or relu_scale_norm or if_concat:
-            raise NotImplementedError("VMG HIP path: ltam/retention_decay/non_linear/gating/symm/relu_scale must be true, "
+        if not (ltam and retention_decay and non_linear and relu_scale) or relu_scale_norm or if_concat:
+            raise NotImplementedError("VMG HIP path: ltam/retention_decay/non_linear/relu_scale must be true, "
                                       "relu_scale_norm/if_concat false (as in all shipped configs)")
-        if symm_act not in ("tanh", nn.Tanh) or traj_mode not in ("wins", "max") or any(m != "mlps" for m in mixer_type[:len(depths) // 2 + 1]):
-            raise NotImplementedError("VMG HIP path: symm_act='tanh', traj_mode 'wins' or 'max', mixer_type='mlps' only")
+        symm_act = symm_act_name(symm_act)  # ValueError for anything but the reference's five (models/vmg.py:265-274)
+        if traj_mode not in ("wins", "max") or any(m != "mlps" for m in mixer_type[:len(depths) // 2 + 1]):
+            raise NotImplementedError("VMG HIP path: traj_mode 'wins' or 'max', mixer_type='mlps' only")
         if back_RBs != 0 or traj_refine is not None:
             raise NotImplementedError("back_RBs > 0 / traj_refine are not used by any shipped config")
         self.num_layers = len(depths)
@@ -712,7 +756,7 @@ class VMG(nn.Module):
         def stage(dim, depth, heads, ch, cw, dpr, ws, nk, al, rn, th):
             return Mlp_encoder(dim, depth, heads, ch, cw, mlp_ratio, n_groups, qkv_bias, dpr, ws, nk, al, temporal_empty, rn, th,
                                flow_smooth, smooth_region_range, ffn_type, r_scaling, twins, traj_scale, m_scaling, if_local_fuse,
-                               channel_mixer, traj_mode)
+                               channel_mixer, traj_mode, gating, symm, symm_act)
 
         self.encoder_layers, self.upsample, self.downsample = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         for i in range(self.num_enc_layers):
