@@ -342,6 +342,8 @@ int vmg_layernorm_fwd(int dtype, const void* x, const float* w, const float* b, 
 /* LayerNorm backward: dx = [add +] the input gradient for the SUM of ndy (1..5) gradients dy[i] of the LayerNorm output; dw / db are added to.
  *   dy[i]  contiguous (M, C) rows, 16-byte aligned; summed in fp32 inside the kernel (a normalised tensor read by several consumers -- the
  *          MorphFC mixer reads LayerNorm(x) five times -- gets one gradient per consumer; autograd would add them pairwise, three passes per add).
+ *   x, dx  contiguous (M, C) rows (or the feature map of the space<->depth forms), 16-byte aligned like dy: all three are read / written
+ *          with the same vectors, and a misaligned one is refused before anything is launched.
  *   add    contiguous (M, C) in the activation dtype, 16-byte aligned, or null: the gradient that reaches the normalised tensor through a skip
  *          connection (TAB: x feeds norm2 / norm3 AND the residual, models/function.py:1212-1217) is summed here instead of by a separate pass.
  *   ws     null, or vmg_layernorm_bwd_ws_bytes() bytes of device memory, 16-byte aligned, ALL ZERO before its first use.  Every launch leaves it

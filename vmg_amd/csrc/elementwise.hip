@@ -925,6 +925,7 @@ static int ln_bwd_impl(int dtype, const void* dy, const void* x, const float* me
                        const LnMore more = LnMore{{nullptr, nullptr, nullptr, nullptr}, 0}) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "layernorm_bwd: bad dtype");
   VMG_CHECK(dy && x && mean && rstd && w && dx && dw && db && M > 0 && C > 0, "layernorm_bwd: bad arguments");
+  VMG_CHECK(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dx) % 16 == 0, "layernorm_bwd: dy, x and dx must be 16-byte aligned");
   VMG_CHECK((uintptr_t)ws % 16 == 0, "layernorm_bwd: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   int v = ln_vec(dtype, C);

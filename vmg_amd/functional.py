@@ -705,9 +705,18 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], 
     return y
 
 
+def _ln_aligned(t):
+    """t on a 16-byte boundary, as the LayerNorm kernels read it (contiguity is the kernel wrappers' business).  A contiguous view at an odd row offset (x[1:] of 72-byte
+    rows) is contiguous but not aligned, and the kernels refuse it: such a tensor is copied to storage of its own (torch's allocations are
+    aligned); every other one is returned as it is (one pointer test per tensor on the common path)."""
+    if t is None or not t.data_ptr() & 15:
+        return t
+    return t.clone() if t.is_contiguous() else t.contiguous()
+
+
 def _ln_forward(ctx, x, w, b, eps, mode=None):
-    """Forward of every LayerNorm node: (y, contiguous x).  mode: the space<->depth map ('down' / 'up') of UpdownkeepSampling, or None."""
-    x = x.contiguous()
+    """Forward of every LayerNorm node: (y, contiguous aligned x).  mode: the space<->depth map ('down' / 'up') of UpdownkeepSampling, or None."""
+    x = _ln_aligned(x.contiguous())
     y, mean, rstd = K.layernorm_forward(x, w, b, eps) if mode is None else K.space_depth_ln_forward(x, mode, w, b, eps)
     ctx.mode = mode
     ctx.save_for_backward(x, mean, rstd, w)
@@ -722,6 +731,7 @@ def _ln_backward(ctx, dys, dskip=None):
         DEFERRED.done(ctx)
         return dskip, None, None
     x, mean, rstd, w = ctx.saved_tensors
+    dys, dskip = [_ln_aligned(g) for g in dys], _ln_aligned(dskip)
     if ctx.mode is None:
         dx, dw, db = K.layernorm_backward(dys, x, mean, rstd, w, into=DEFERRED.into(ctx), add=dskip)
     else:
