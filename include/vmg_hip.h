@@ -415,6 +415,42 @@ int vmg_gate_res_fwd(int dtype, int form, int act, const void* a, const void* y,
 int vmg_gate_res_bwd(int dtype, int form, int act, const void* dout, const void* a, const void* y, const float* coef, void* da, void* dy,
                      int64_t rows, int G, int C, void* stream);
 
+/* ---- the patch-shift FFN, Mlp_cnn_shift (ffn_type 'ffn_cnn_shift'; models/function.py PatchShift2D :197-236): csrc/shift_ffn.hip.
+ *   x1 = gelu(fc(x));  h = shift_inv(gelu(fc1(shift(x1))));  w = gelu(fc2(x1));  a = softmax_2(reweight(mean_{T,H,W}(h + w)));  y = proj(h a0 + w a1)
+ * Patch shift on (N, H, W, Cs) channels-last, fp32 / bf16: g = ceil(Cs / 9), channel c belongs to chunk i = c / g, and
+ *   vmg_patch_shift_fwd   y[n, q, c] = f(x[n, q - s d_c, c]),  d_c = (1 - i/3, 1 - i%3) (rows, columns);  zero where that pixel is outside the H x W
+ *                         frame (nothing wraps, nothing moves between the N frames).  s = sign: +1 shift, -1 shift_inv.  act 0: f = identity
+ *                         (a copy: the bits of x);  act 3: f = exact (erf) GELU, evaluated in fp32 on the source element (gelu(0) = 0).
+ *   vmg_patch_shift_bwd   dx[n, q, c] = f'(x[n, q, c]) * dy[n, q + s d_c, c], zero where that pixel is outside.  act 0: the forward with sign -s,
+ *                         the same kernel instance; x is not read and may be null.  act 3 reads x.
+ *   vmg_patch_shift_plan  the route of such a launch, a pure function: VMG_SHIFT_VECTOR (one thread per 16-byte vector of a destination pixel) when
+ *                         g and Cs are multiples of the vector (8 bf16 / 4 fp32) and aligned16 (every pointer on a 16-byte boundary) is non-zero;
+ *                         else VMG_SHIFT_ELEMENT (one thread per element: any g, chunk boundaries anywhere).  -1: bad dtype or Cs < 1.
+ * Two-branch re-weighting, (G, R, C) views as above; the pooled mean of h + w is vmg_group_reduce mode 0.
+ *   vmg_se_mlp2_fwd       m (G, C) fp32 -> pre (G, Hd) = W1 m + b1;  out (G, C, 2) = softmax over each channel's two consecutive logits of
+ *                         W2 gelu(pre) + b2   (W1 (Hd, C), W2 (2C, Hd); b1, b2 may be null)
+ *   vmg_se_mlp2_bwd       dout (G, C, 2) -> dm (G, C) * dm_scale and the four parameter gradients, written (accumulate 0) or added to (1);
+ *                         ws: G * (2C + Hd) floats.  Two launches, rows summed in order, as vmg_se_mlp_bwd.
+ *   vmg_group_reduce2     out (G, C, 2) = scale * sum_r a * {b0, b1}: both branch sums from one pass over a = dy; the two-launch ordered-partials
+ *                         scheme and workspace of vmg_group_reduce3 (the same bits on every run).  C even, <= 512.
+ *   vmg_mix2_fwd          y = h * coef[g, c, 0] + w * coef[g, c, 1]
+ *   vmg_mix2_bwd          dh = dy * coef[g, c, 0] + add[g, c];  dw = dy * coef[g, c, 1] + add[g, c]   (one launch, two outputs)
+ *                         16-byte vectors when C and the pointers allow, else pairs of elements (C even).
+ * Non-zero (vmg_last_error) on a null pointer, a pointer not aligned to what the chosen kernel reads, N, H, W, Cs < 1, a sign other than +-1. */
+#define VMG_SHIFT_VECTOR 1
+#define VMG_SHIFT_ELEMENT 2
+int vmg_patch_shift_plan(int dtype, int Cs, int aligned16);
+int vmg_patch_shift_fwd(int dtype, int sign, int act, const void* x, void* y, int N, int H, int W, int Cs, void* stream);
+int vmg_patch_shift_bwd(int dtype, int sign, int act, const void* dy, const void* x, void* dx, int N, int H, int W, int Cs, void* stream);
+int vmg_se_mlp2_fwd(const float* m, const float* w1, const float* b1, const float* w2, const float* b2, float* pre, float* out, int G, int C, int Hd,
+                    void* stream);
+int vmg_se_mlp2_bwd(const float* dout, const float* out, const float* m, const float* pre, const float* w1, const float* w2, float* dm, float* dw1,
+                    float* db1, float* dw2, float* db2, float* ws, int G, int C, int Hd, float dm_scale, int accumulate, void* stream);
+int vmg_group_reduce2(int dtype, const void* a, const void* b0, const void* b1, float* out, int G, int64_t R, int C, float scale, float* ws,
+                      int64_t ws_bytes, void* stream);
+int vmg_mix2_fwd(int dtype, const void* h, const void* w, const float* coef, void* y, int64_t rows, int64_t R, int C, void* stream);
+int vmg_mix2_bwd(int dtype, const void* dy, const float* coef, const float* add, void* dh, void* dw, int64_t rows, int64_t R, int C, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Flow-guided sampling of the trajectory recurrence (models/trajectory.py:71-116 flow_warp, :329-333, :414-417).
  * flow: (N,H,W,2) fp32 pixel offsets (x then y); coordinates follow flow_warp + F.grid_sample(align_corners=True).

@@ -1214,6 +1214,70 @@ def reweight_mix(h, w, c, fc1w, fc1b, fc2w, fc2b):
     return _ReweightMix.apply(h, w, c, fc1w, fc1b, fc2w, fc2b)
 
 
+class _ReweightMix2(_Fn):
+    """Softmax re-weighting of the two branches of Mlp_cnn_shift: a = softmax_2(Mlp(mean_{T,H,W}(h + w)));  y = h*a0 + w*a1 (csrc/shift_ffn.hip)."""
+
+    @staticmethod
+    def forward(ctx, h, w, fc1w, fc1b, fc2w, fc2b):
+        h, w = _ln_aligned(h.contiguous()), _ln_aligned(w.contiguous())
+        B, C = h.shape[0], h.shape[-1]
+        R = h.numel() // (B * C)
+        m = K.group_reduce(h, B, b=w, scale=1.0 / R)
+        pre, a = K.se_mlp2_forward(m, fc1w, fc1b, fc2w, fc2b)  # a (B, 2C) = (B, C, 2): softmax over each channel's two logits
+        y = K.mix2_forward(h, w, a, B)
+        ctx.R = R
+        ctx.save_for_backward(h, w, a, m, pre, fc1w, fc2w)
+        DEFERRED.claim(ctx, fc1w, fc1b, fc2w, fc2b)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        h, w, a, m, pre, fc1w, fc2w = ctx.saved_tensors
+        R = ctx.R
+        dy = _ln_aligned(dy.contiguous())
+        B, C = h.shape[0], h.shape[-1]
+        da = K.group_reduce2(dy, h, w, B).reshape(B, 2 * C)  # (B,C,2): d loss / d softmax weights, one pass over dy
+        dm, dw1, db1, dw2, db2 = K.se_mlp2_backward(da, a, m, pre, fc1w, fc2w, 1.0 / R, into=DEFERRED.into(ctx))  # softmax, Linear, GELU, Linear backward
+        dh, dw = K.mix2_backward(dy, a, dm, B)
+        DEFERRED.done(ctx)
+        if ctx.direct:
+            return dh, dw, None, None, None, None
+        return dh, dw, dw1, db1, dw2, db2
+
+
+def reweight_mix2(h, w, fc1w, fc1b, fc2w, fc2b):
+    """h, w (B, ..., C): the two-branch re-weighting of Mlp_cnn_shift; the pooled mean runs over everything between the first and the last dimension."""
+    return _ReweightMix2.apply(h, w, fc1w, fc1b, fc2w, fc2b)
+
+
+class _PatchShift(_Fn):
+    """PatchShift2D (models/function.py:197-236) or its inverse on (N, H, W, Cs), optionally of gelu(x): one launch each way (csrc/shift_ffn.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, sign, gelu):
+        x = _ln_aligned(x.contiguous())
+        ctx.sign, ctx.gelu = sign, gelu
+        if gelu:
+            ctx.save_for_backward(x)
+        return K.patch_shift_forward(x, sign, gelu)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _ln_aligned(dy.contiguous())
+        return K.patch_shift_backward(dy, ctx.sign, ctx.saved_tensors[0] if ctx.gelu else None), None, None
+
+
+def patch_shift(x: torch.Tensor, inverse: bool = False, act: Optional[str] = None) -> torch.Tensor:
+    """shift(f(x)), or shift_inv(f(x)) with inverse, of x (B, T, H, W, C) or (N, H, W, C): channel chunk i = c // ceil(C / 9) moves by
+    (1 - i // 3, 1 - i % 3) pixels (the opposite way with inverse), zero-filled, each frame on its own.  act: None (f = identity) or 'gelu'."""
+    if act not in (None, "gelu"):
+        raise ValueError(f"patch_shift: act is None or 'gelu', got {act!r}")
+    if x.dim() not in (4, 5):
+        raise ValueError(f"patch_shift: (B, T, H, W, C) or (N, H, W, C) expected, got {tuple(x.shape)}")
+    y = _PatchShift.apply(x.reshape(-1, *x.shape[-3:]), -1 if inverse else 1, act == "gelu")
+    return y.reshape(x.shape)
+
+
 class _TanhGate(_Fn):
     """(x + y) * tanh(y) (models/function.py:801-802)."""
 

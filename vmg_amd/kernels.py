@@ -1441,6 +1441,145 @@ def se_mlp_backward(dout: torch.Tensor, out: torch.Tensor, m: torch.Tensor, pre:
     return dm.view(G, C), dw1.view(Hd, C), db1, dw2.view(Co, Hd), db2
 
 
+# ---- the patch-shift FFN (csrc/shift_ffn.hip)
+SHIFT_ROUTES = {hip.SHIFT_VECTOR: "vector", hip.SHIFT_ELEMENT: "element"}
+
+
+def patch_shift_route(Cs: int, dtype: torch.dtype, aligned: bool = True) -> str:
+    """The kernel a patch shift of Cs channels runs on (vmg_patch_shift_plan, the function the entries themselves call; no device needed):
+    'vector' when the chunk width ceil(Cs / 9) and Cs are multiples of the 16-byte vector and the pointers are 16-byte aligned, else 'element'."""
+    r = hip.lib().vmg_patch_shift_plan(hip.dtype_code(dtype), int(Cs), int(bool(aligned)))
+    if r not in SHIFT_ROUTES:
+        raise HipError(f"patch_shift_route: no route for Cs = {Cs}, {dtype}")
+    return SHIFT_ROUTES[r]
+
+
+def _shift_args(who, x, others):
+    hip.require_cuda(x, *others)
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous():
+        raise HipError(f"{who}: a contiguous fp32 / bf16 (N, H, W, Cs) tensor expected")
+    if any(t.shape != x.shape or t.dtype != x.dtype or not t.is_contiguous() for t in others):
+        raise HipError(f"{who}: contiguous operands of one shape / dtype expected")
+    if min(x.shape) < 1:
+        raise HipError(f"{who}: empty tensor")
+
+
+def patch_shift_forward(x: torch.Tensor, sign: int, gelu: bool = False) -> torch.Tensor:
+    """PatchShift2D (sign +1) / its inverse (-1) of x (N, H, W, Cs), with gelu: of gelu(x) (vmg_patch_shift_fwd)."""
+    _shift_args("patch_shift_forward", x, [])
+    N, H, W, Cs = x.shape
+    y = torch.empty_like(x)
+    hip.check(hip.lib().vmg_patch_shift_fwd(hip.dtype_code(x.dtype), int(sign), hip.ACT_GELU if gelu else hip.ACT_NONE, x.data_ptr(), y.data_ptr(), N, H, W, Cs,
+                                            hip.stream_ptr()), "vmg_patch_shift_fwd")
+    return y
+
+
+def patch_shift_backward(dy: torch.Tensor, sign: int, x: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The input gradient of patch_shift_forward(x, sign, gelu): x given = the GELU form (vmg_patch_shift_bwd)."""
+    _shift_args("patch_shift_backward", dy, [x] if x is not None else [])
+    N, H, W, Cs = dy.shape
+    dx = torch.empty_like(dy)
+    hip.check(hip.lib().vmg_patch_shift_bwd(hip.dtype_code(dy.dtype), int(sign), hip.ACT_GELU if x is not None else hip.ACT_NONE, dy.data_ptr(),
+                                            x.data_ptr() if x is not None else None, dx.data_ptr(), N, H, W, Cs, hip.stream_ptr()), "vmg_patch_shift_bwd")
+    return dx
+
+
+def group_reduce2(a: torch.Tensor, b0: torch.Tensor, b1: torch.Tensor, G: int, scale: float = 1.0) -> torch.Tensor:
+    """fp32 (G, C, 2): scale * sum_r a * {b0, b1} over the rows of each group, one pass over a."""
+    hip.require_cuda(a, b0, b1)
+    C = a.shape[-1]
+    rows = a.numel() // C
+    if G <= 0 or rows % G or any(t.shape != a.shape or t.dtype != a.dtype or not t.is_contiguous() for t in (a, b0, b1)):
+        raise HipError("group_reduce2: contiguous tensors of one shape / dtype covering G groups expected")
+    out = torch.empty((G, C, 2), dtype=torch.float32, device=a.device)
+    ws = _workspace("vmg_group_reduce_ws_bytes", a.device)
+    hip.check(hip.lib().vmg_group_reduce2(hip.dtype_code(a.dtype), a.data_ptr(), b0.data_ptr(), b1.data_ptr(), out.data_ptr(), G, rows // G, C, scale,
+                                          ws.data_ptr(), ws.numel(), hip.stream_ptr()), "vmg_group_reduce2")
+    return out
+
+
+def mix2_forward(h: torch.Tensor, w: torch.Tensor, coef: torch.Tensor, G: int) -> torch.Tensor:
+    """h * coef[g, c, 0] + w * coef[g, c, 1], coef (G, C, 2) fp32 (vmg_mix2_fwd)."""
+    hip.require_cuda(h, w, coef)
+    C = h.shape[-1]
+    rows = h.numel() // C
+    if G <= 0 or rows % G or w.shape != h.shape or w.dtype != h.dtype or not (h.is_contiguous() and w.is_contiguous()):
+        raise HipError("mix2_forward: contiguous operands of one shape / dtype covering G groups expected")
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() != G * C * 2:
+        raise HipError(f"mix2_forward: coef must be contiguous fp32 of G*C*2 = {G * C * 2} elements")
+    y = torch.empty_like(h)
+    hip.check(hip.lib().vmg_mix2_fwd(hip.dtype_code(h.dtype), h.data_ptr(), w.data_ptr(), coef.data_ptr(), y.data_ptr(), rows, rows // G, C,
+                                     hip.stream_ptr()), "vmg_mix2_fwd")
+    return y
+
+
+def mix2_backward(dy: torch.Tensor, coef: torch.Tensor, add: torch.Tensor, G: int):
+    """(dy * coef[g, c, 0] + add[g, c], dy * coef[g, c, 1] + add[g, c]) in one launch (vmg_mix2_bwd)."""
+    hip.require_cuda(dy, coef, add)
+    C = dy.shape[-1]
+    rows = dy.numel() // C
+    if G <= 0 or rows % G or not dy.is_contiguous():
+        raise HipError("mix2_backward: a contiguous gradient covering G groups expected")
+    for t, n in ((coef, G * C * 2), (add, G * C)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise HipError("mix2_backward: coef (G, C, 2) and add (G, C) must be contiguous fp32")
+    dh, dw = torch.empty_like(dy), torch.empty_like(dy)
+    hip.check(hip.lib().vmg_mix2_bwd(hip.dtype_code(dy.dtype), dy.data_ptr(), coef.data_ptr(), add.data_ptr(), dh.data_ptr(), dw.data_ptr(), rows,
+                                     rows // G, C, hip.stream_ptr()), "vmg_mix2_bwd")
+    return dh, dw
+
+
+def se_mlp2_forward(m: torch.Tensor, w1: torch.Tensor, b1, w2: torch.Tensor, b2):
+    """The re-weighting MLP of Mlp_cnn_shift on pooled rows m (G, C) fp32: returns (pre (G, Hd), a (G, 2C) = (G, C, 2): softmax over each channel's two logits)."""
+    hip.require_cuda(m, w1, w2, b1, b2)
+    G, C = m.shape
+    Hd = w1.shape[0]
+    for t in (m, w1, w2, b1, b2):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise HipError("se_mlp2: contiguous fp32 tensors only")
+    if tuple(w1.shape) != (Hd, C) or tuple(w2.shape) != (2 * C, Hd):
+        raise HipError(f"se_mlp2: W1 ({Hd}, {C}) and W2 ({2 * C}, {Hd}) expected")
+    pre = torch.empty(G, Hd, dtype=torch.float32, device=m.device)
+    out = torch.empty(G, 2 * C, dtype=torch.float32, device=m.device)
+    hip.check(hip.lib().vmg_se_mlp2_fwd(m.data_ptr(), w1.data_ptr(), b1.data_ptr() if b1 is not None else None, w2.data_ptr(),
+                                        b2.data_ptr() if b2 is not None else None, pre.data_ptr(), out.data_ptr(), G, C, Hd, hip.stream_ptr()), "vmg_se_mlp2_fwd")
+    return pre, out
+
+
+def se_mlp2_backward(dout: torch.Tensor, out: torch.Tensor, m: torch.Tensor, pre: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, dm_scale: float, into=None):
+    """-> dm (G, C) * dm_scale, dw1, db1, dw2, db2 (fresh tensors); into = (gw1, gb1, gw2, gb2): the parameter gradients are ADDED to these
+    contiguous fp32 buffers (param.grad) and returned as such -- se_mlp_backward's contract."""
+    hip.require_cuda(dout, out, m, pre, w1, w2)
+    G, C = m.shape
+    Hd, Co = w1.shape[0], 2 * C
+    for t in (dout, out, m, pre, w1, w2):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise HipError("se_mlp2: contiguous fp32 tensors only")
+    if dout.numel() != G * Co or out.numel() != G * Co or tuple(w2.shape) != (Co, Hd):
+        raise HipError("se_mlp2: dout and out (G, 2C), W2 (2C, Hd) expected")
+    sizes = (G * C, G * (Co + Hd)) if into is not None else (G * C, G * (Co + Hd), Hd * C, Hd, Co * Hd, Co)
+    buf = torch.empty(sum(sizes), dtype=torch.float32, device=m.device)
+    o = 0
+    parts = []
+    for n in sizes:
+        parts.append(buf[o:o + n])
+        o += n
+    if into is not None:
+        dm, ws = parts
+        dw1, db1, dw2, db2 = into
+        for t, n in zip(into, (Hd * C, Hd, Co * Hd, Co)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
+                raise HipError("se_mlp2: gradient buffers must be contiguous fp32 of the parameters' sizes")
+    else:
+        dm, ws, dw1, db1, dw2, db2 = parts
+    hip.check(hip.lib().vmg_se_mlp2_bwd(dout.data_ptr(), out.data_ptr(), m.data_ptr(), pre.data_ptr(), w1.data_ptr(), w2.data_ptr(), dm.data_ptr(),
+                                        dw1.data_ptr(), db1.data_ptr(), dw2.data_ptr(), db2.data_ptr(), ws.data_ptr(), G, C, Hd, float(dm_scale),
+                                        1 if into is not None else 0, hip.stream_ptr()), "vmg_se_mlp2_bwd")
+    if into is not None:
+        return dm.view(G, C), dw1, db1, dw2, db2
+    return dm.view(G, C), dw1.view(Hd, C), db1, dw2.view(Co, Hd), db2
+
+
 class PackPlan:
     """One-launch repacking of many weights (vmg_pack_entry / vmg_pack_run): the entry array lives on the device and is rebuilt only
     when the set of packs (or a weight's / pack buffer's address) changes."""

@@ -240,6 +240,46 @@ class Mlp_cnn(nn.Module):
         return lin(self.fc2, h, res=res, fuse_src_act=True).reshape(B, T, H, W, C)
 
 
+class PatchShift2D(nn.Module):
+    """The reference's parameter-free shift module (models/function.py:197-236): channel chunk i of nine moves by (1 - i // 3, 1 - i % 3) pixels,
+    the other way with inv, zero-filled.  Held by Mlp_cnn_shift for the module tree; the FFN calls functional.patch_shift itself."""
+
+    def __init__(self, inv=False):
+        super().__init__()
+        self.inv = bool(inv)
+
+    def forward(self, x):
+        return FH.patch_shift(x, inverse=self.inv)
+
+
+class Mlp_cnn_shift(nn.Module):
+    """The patch-shift FFN (reference: models/function.py Mlp_cnn_shift), hidden = int(C * exp_r):
+    x1 = gelu(fc(x));  h = shift_inv(gelu(fc1(shift(x1))));  w = gelu(fc2(x1));  a = softmax_2(reweight(mean_{T,H,W}(h + w)));  proj(h a0 + w a1).
+    The Linears are the 1x1 kernel with its GELU epilogue; both shifts, the second GELU and the two-branch re-weighting are csrc/shift_ffn.hip."""
+
+    def __init__(self, in_features, exp_r=4):
+        super().__init__()
+        self.hidden_features = int(in_features * exp_r)
+        self.fc = nn.Linear(in_features, self.hidden_features)
+        self.shift = PatchShift2D(inv=False)
+        self.fc1 = nn.Linear(self.hidden_features, in_features)
+        self.shift_inv = PatchShift2D(inv=True)
+        self.act = nn.GELU()
+        self.fc2 = nn.Linear(self.hidden_features, in_features)
+        self.reweight = Mlp(in_features, in_features // 4, in_features * 2)
+        self.proj = nn.Linear(in_features, in_features)
+        self.drop = nn.Dropout(0.0)
+
+    def forward(self, x):
+        x1 = lin(self.fc, x, act=ACT_GELU)
+        xa, xb = FH.fan_out(x1, 2)  # two consumers: their gradients meet in one sum
+        u = lin(self.fc1, FH.patch_shift(xa))
+        h = FH.patch_shift(u, inverse=True, act="gelu")  # the GELU rides on the inverse shift's pass
+        w = lin(self.fc2, xb, act=ACT_GELU)
+        rw = self.reweight
+        return lin(self.proj, FH.reweight_mix2(h, w, rw.fc1.weight, rw.fc1.bias, rw.fc2.weight, rw.fc2.bias))
+
+
 class sigmoid_symm(nn.Module):
     """sigmoid(x) - 0.5: the reference's symmetric sigmoid (models/function.py:18-27), parameter-free."""
 
@@ -365,8 +405,13 @@ class TAB(nn.Module):
             self.channel_mixing = Mlp(embed_dim, int(embed_dim * mlp_ratio))
         elif ffn == "ffn_cnn":
             self.channel_mixing = Mlp_cnn(embed_dim, exp_r=mlp_ratio, n_groups=n_groups)
+        elif ffn == "ffn_cnn_shift":
+            self.channel_mixing = Mlp_cnn_shift(embed_dim, exp_r=mlp_ratio)
+        elif ffn in ("irffn_single", "irffn_multi"):
+            raise NotImplementedError(f"ffn_type {ffn!r}: the reference cannot run it either (Mlp_ir cannot be constructed through TAB, Mlp_ir_multi's "
+                                      "forward raises on its first call); 'vanilla', 'ffn_cnn' or 'ffn_cnn_shift'")
         else:
-            raise NotImplementedError(f"ffn_type {ffn!r} is not used by any shipped config")
+            raise NotImplementedError(f"ffn_type {ffn!r}: 'vanilla', 'ffn_cnn' or 'ffn_cnn_shift' (the reference cannot run any other value either)")
         self.drop_prob = float(drop_path)
 
     def forward(self, x):
