@@ -560,6 +560,13 @@ double vmg_prof_null_interval_us(int reps, void* stream);
 int vmg_morphfc_fwd(int axis, int chunk, const void* x, const void* relu_mask, const void* packed, const float* bias, void* out, void* tok_out,
                     int BT, int H, int W, int C, int Cp, int cout_tiles, int relu, float in_scale, float out_scale, void* stream);
 int64_t vmg_morphfc_token_rows(int axis, int chunk, int BT, int H, int W);
+/* What vmg_morphfc_fwd launches for a geometry on a device of `ncu` compute units -- the function the entry point dispatches through (pure: no
+ * device query, no pointer but `plan`): plan = {NK, NCT, EVEN, MASK, ngroups, ntiles, nwg, lds_bytes}: the morph_linear_kernel<NK, NCT, EVEN,
+ * MASK> instance (NK = ceil(Cp / 32) k-steps, NCT = ceil(Cp / 16) output tiles, EVEN: S = Cp / chunk is even, MASK: the data-gradient form),
+ * the groups of `chunk` positions, the 16-token tiles (one per wave and trip), the workgroups (8 waves each, at most ncu) and the dynamic LDS
+ * size.  Nonzero (vmg_last_error) for what the kernel does not serve. */
+enum { VMG_MORPHFC_PLAN_INTS = 8 };
+int vmg_morphfc_plan(int axis, int chunk, int BT, int H, int W, int C, int Cp, int has_mask, int ncu, int* plan);
 /* General MorphFC path (any chunk / Cp, bf16 and fp32; the full configuration's chunk 12, Cp 224 / 228 / 448 -- models/function.py:749-750,
  * 763-764, 772, 776-777, 785): the token matrix of the reference's pad + rearrange chain written by ONE gather kernel, and turned back into the
  * feature map (cropped) by ONE scatter kernel; the Linear in between is vmg_conv_fwd (ks = 1).  x / out: (BT, H, W, C) channels-last; tok:
@@ -569,6 +576,10 @@ int64_t vmg_morphfc_token_rows(int axis, int chunk, int BT, int H, int W);
 int64_t vmg_morph_token_rows(int axis, int chunk, int BT, int H, int W);
 int vmg_morph_tokens_gather(int dtype, int axis, int chunk, const void* x, void* tok, int BT, int H, int W, int C, int Cp, int ld, void* stream);
 int vmg_morph_tokens_scatter(int dtype, int axis, int chunk, const void* tok, void* out, int BT, int H, int W, int C, int Cp, int ld, void* stream);
+/* The kernel both token calls run (they dispatch through it; pure): 1 = LDS-tiled, one workgroup per group -- C and ld multiples of the 16-byte
+ * vector (8 bf16 / 4 fp32 elements), chunk * ld elements within 64 KiB, and `aligned`: both pointers 16-byte aligned --, 0 = element-wise;
+ * negative for a bad dtype / geometry. */
+int vmg_morph_tokens_route(int dtype, int chunk, int C, int ld, int aligned);
 
 /* ---- 3-D shifted-window attention (reference: models/swin_3d.py:167-252 rWindowAttention.attention, :55-118 window partition / mask, :772-832 block) ----
  * q (B, D, H, W, C) and kv (B, D, H, W, 2C; k then v) are the outputs of the q / kv Linears on the UN-partitioned feature map; window partition

@@ -406,14 +406,23 @@ extern "C" int64_t vmg_morph_token_rows(int axis, int chunk, int BT, int H, int 
   return (int64_t)BT * (axis == 0 ? W : H) * cdiv(axis == 0 ? H : W, chunk) * chunk;
 }
 
+// The kernel the two token calls run (the rule, in one place): 1 = LDS-tiled (one workgroup per group: whole 16-byte vectors of the pixel and token rows, the
+// group's chunk x ld tile within 64 KiB, 16-byte aligned pointers), 0 = element-wise.  Pure: nothing is queried or dereferenced.
+extern "C" int vmg_morph_tokens_route(int dtype, int chunk, int C, int ld, int aligned) {
+  VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "morph_tokens_route: bad dtype");
+  VMG_CHECK(chunk > 0 && C > 0 && ld > 0, "morph_tokens_route: bad geometry");
+  const int es = dtype == VMG_BF16 ? 2 : 4, vn = 16 / es;
+  const long long lds = (long long)chunk * ld * es;
+  return (C % vn == 0 && ld % vn == 0 && lds <= 64 * 1024 && aligned) ? 1 : 0;
+}
+
 extern "C" int vmg_morph_tokens_gather(int dtype, int axis, int chunk, const void* x, void* tok, int BT, int H, int W, int C, int Cp, int ld, void* stream) {
   VMG_CHECK(dtype == VMG_F32 || dtype == VMG_BF16, "morph_tokens_gather: bad dtype");
   VMG_CHECK(x && tok, "morph_tokens_gather: null pointer");
   TokGeo g;
   if (int rc = tok_geo(g, axis, chunk, BT, H, W, C, Cp, ld)) return rc;
-  const int es = dtype == VMG_BF16 ? 2 : 4, vn = 16 / es;
-  const long long lds = (long long)chunk * ld * es;
-  if (C % vn == 0 && ld % vn == 0 && lds <= 64 * 1024 && ((uintptr_t)x | (uintptr_t)tok) % 16 == 0) {  // the LDS-tiled form (one workgroup per group)
+  const long long lds = (long long)chunk * ld * (dtype == VMG_BF16 ? 2 : 4);
+  if (vmg_morph_tokens_route(dtype, chunk, C, ld, ((uintptr_t)x | (uintptr_t)tok) % 16 == 0) == 1) {  // the LDS-tiled form (one workgroup per group)
     const int gb = (int)(g.ngroups > 16384 ? 16384 : g.ngroups);
     if (dtype == VMG_BF16) hipLaunchKernelGGL(morph_gather_lds_kernel<bf16>, dim3(gb), dim3(256), (size_t)lds, (hipStream_t)stream, (const bf16*)x, (bf16*)tok, g);
     else hipLaunchKernelGGL(morph_gather_lds_kernel<float>, dim3(gb), dim3(256), (size_t)lds, (hipStream_t)stream, (const float*)x, (float*)tok, g);
@@ -433,9 +442,8 @@ extern "C" int vmg_morph_tokens_scatter(int dtype, int axis, int chunk, const vo
   VMG_CHECK(tok && out, "morph_tokens_scatter: null pointer");
   TokGeo g;
   if (int rc = tok_geo(g, axis, chunk, BT, H, W, C, Cp, ld)) return rc;
-  const int es = dtype == VMG_BF16 ? 2 : 4, vn = 16 / es;
-  const long long lds = (long long)chunk * ld * es;
-  if (C % vn == 0 && ld % vn == 0 && lds <= 64 * 1024 && ((uintptr_t)out | (uintptr_t)tok) % 16 == 0) {  // the LDS-tiled form (one workgroup per group)
+  const long long lds = (long long)chunk * ld * (dtype == VMG_BF16 ? 2 : 4);
+  if (vmg_morph_tokens_route(dtype, chunk, C, ld, ((uintptr_t)out | (uintptr_t)tok) % 16 == 0) == 1) {  // the LDS-tiled form (one workgroup per group)
     const int gb = (int)(g.ngroups > 16384 ? 16384 : g.ngroups);
     if (dtype == VMG_BF16) hipLaunchKernelGGL(morph_scatter_lds_kernel<bf16>, dim3(gb), dim3(256), (size_t)lds, (hipStream_t)stream, (const bf16*)tok, (bf16*)out, g);
     else hipLaunchKernelGGL(morph_scatter_lds_kernel<float>, dim3(gb), dim3(256), (size_t)lds, (hipStream_t)stream, (const float*)tok, (float*)out, g);
@@ -460,38 +468,57 @@ extern "C" int64_t vmg_morphfc_token_rows(int axis, int chunk, int BT, int H, in
   return cdiv64(ngroups, 16 / chunk) * 16;
 }
 
+// What vmg_morphfc_fwd launches for a geometry (the rule, in one place; pure: no device query, no pointer): plan = {NK, NCT, EVEN, MASK, ngroups, ntiles, nwg,
+// lds_bytes} -- the morph_linear_kernel<NK, NCT, EVEN, MASK> instance, the groups and 16-token tiles, the grid and the dynamic LDS size.
+extern "C" int vmg_morphfc_plan(int axis, int chunk, int BT, int H, int W, int C, int Cp, int has_mask, int ncu, int* plan) {
+  VMG_CHECK(plan && BT > 0 && H > 0 && W > 0 && ncu > 0, "morphfc: bad arguments");
+  VMG_CHECK(axis == 0 || axis == 1, "morphfc: axis 0 (H) or 1 (W)");
+  VMG_CHECK((chunk == 8 || chunk == 16) && Cp % chunk == 0 && Cp >= C && C > 0 && C % 8 == 0 && chunk * (C / 8) <= 64 * MF_MAXK,
+            "morphfc: chunk must be 8 or 16 and divide Cp; C a multiple of 8, at most %d", 64 * MF_MAXK * 8 / 16);
+  const int nk = (Cp + 31) / 32, nct = (Cp + 15) / 16;
+  const int len = axis == 0 ? H : W, lines = axis == 0 ? W : H;
+  const long long ngroups = (long long)BT * lines * cdiv(len, chunk);
+  VMG_CHECK(ngroups < (1LL << 31) - 2, "morphfc: too many groups");
+  const long long ntiles = cdiv64(ngroups, 16 / chunk);
+  const int blkb = (16 * Cp * 2 + 15) & ~15;
+  const int lds = ((nk + 1) / 2) * morph_stage_stride(nct) + nct * 16 * 4 + MF_WAVES * (2 * blkb + 16);
+  VMG_CHECK(lds <= 160 * 1024, "morphfc: Cp = %d needs %d B of LDS (> 160 KiB): use the unfused path", Cp, lds);
+  long long nwg = cdiv64(ntiles, MF_WAVES);
+  if (nwg > ncu) nwg = ncu;  // one workgroup per CU (the LDS holds the weights): tiles are strided over the waves
+  const bool inst = (nk == 5 && nct == 9) || (nk == 4 && nct == 7) || (nk == 1 && nct == 1) || (nk == 1 && nct == 2) || (nk == 2 && nct == 4);
+  if (!inst) {
+    vmg_set_error("morphfc: Cp = %d is not instantiated (144, 112, 64, 32, 16)", Cp);
+    return -1;
+  }
+  plan[0] = nk; plan[1] = nct; plan[2] = (Cp / chunk) % 2 == 0; plan[3] = has_mask != 0;
+  plan[4] = (int)ngroups; plan[5] = (int)ntiles; plan[6] = (int)nwg; plan[7] = lds;
+  return 0;
+}
+
 extern "C" int vmg_morphfc_fwd(int axis, int chunk, const void* x, const void* relu_mask, const void* packed, const float* bias, void* out, void* tok_out,
                                int BT, int H, int W, int C, int Cp, int cout_tiles, int relu, float in_scale, float out_scale, void* stream) {
   VMG_CHECK(x && packed && out && BT > 0 && H > 0 && W > 0, "morphfc: bad arguments");
-  VMG_CHECK(axis == 0 || axis == 1, "morphfc: axis 0 (H) or 1 (W)");
-  VMG_CHECK((chunk == 8 || chunk == 16) && Cp % chunk == 0 && Cp >= C && C % 8 == 0 && chunk * (C / 8) <= 64 * MF_MAXK,
-            "morphfc: chunk must be 8 or 16 and divide Cp; C a multiple of 8, at most %d", 64 * MF_MAXK * 8 / 16);
+  int plan[VMG_MORPHFC_PLAN_INTS];
+  if (int rc = vmg_morphfc_plan(axis, chunk, BT, H, W, C, Cp, relu_mask != nullptr, vmg_cu_count(vmg_current_device()), plan)) return rc;
   VMG_CHECK(((uintptr_t)x | (uintptr_t)out | (uintptr_t)packed | (uintptr_t)relu_mask | (uintptr_t)tok_out) % 16 == 0, "morphfc: pointers must be 16-byte aligned");
   VMG_CHECK(!tok_out || Cp % 8 == 0, "morphfc: the token output needs Cp to be a multiple of 8");
-  const int nk = (Cp + 31) / 32, nct = (Cp + 15) / 16;
+  const int nk = plan[0], nct = plan[1], lds = plan[7];
+  const bool even = plan[2] != 0, masked = plan[3] != 0;
   VMG_CHECK(cout_tiles == nct, "morphfc: the pack must hold all %d output tiles in one block (cout_tiles = %d given)", nct, cout_tiles);
   MorphK k;
   memset(&k, 0, sizeof(k));
   k.x = (const bf16*)x; k.mask = (const bf16*)relu_mask; k.out = (bf16*)out; k.tok_out = (bf16*)tok_out; k.wpack = (const char*)packed; k.bias = bias;
   k.BT = BT; k.H = H; k.W = W; k.C = C; k.Cp = Cp; k.chunk = chunk; k.S = Cp / chunk; k.axis = axis;
-  const int len = axis == 0 ? H : W, lines = axis == 0 ? W : H;
-  k.gpl = cdiv(len, chunk);
-  k.ngroups = (long long)BT * lines * k.gpl;
-  VMG_CHECK(k.ngroups < (1LL << 31) - 2, "morphfc: too many groups");
-  const int G = 16 / chunk;
-  k.ntiles = cdiv64(k.ngroups, G);
+  k.gpl = cdiv(axis == 0 ? H : W, chunk);
+  k.ngroups = plan[4];
+  k.ntiles = plan[5];
   k.relu = relu; k.in_scale = in_scale; k.out_scale = out_scale;
   k.ss = morph_stage_stride(nct);
-  const int blkb = (16 * Cp * 2 + 15) & ~15;
-  const int lds = ((nk + 1) / 2) * k.ss + nct * 16 * 4 + MF_WAVES * (2 * blkb + 16);
-  VMG_CHECK(lds <= 160 * 1024, "morphfc: Cp = %d needs %d B of LDS (> 160 KiB): use the unfused path", Cp, lds);
   hipStream_t st = (hipStream_t)stream;
-  const int ncu = vmg_cu_count(vmg_current_device());
-  long long nwg = cdiv64(k.ntiles, MF_WAVES);
-  if (nwg > ncu) nwg = ncu;  // one workgroup per CU (the LDS holds the weights): tiles are strided over the waves
+  const int nwg = plan[6];
 #define MF_CASE(NK_, NCT_) MF_CASE2(NK_, NCT_, true, true) MF_CASE2(NK_, NCT_, false, true) MF_CASE2(NK_, NCT_, true, false) MF_CASE2(NK_, NCT_, false, false)
 #define MF_CASE2(NK_, NCT_, EV_, MK_)                                                                               \
-  if (nk == NK_ && nct == NCT_ && (k.S % 2 == 0) == EV_ && (relu_mask != nullptr) == MK_) {                         \
+  if (nk == NK_ && nct == NCT_ && even == EV_ && masked == MK_) {                                                   \
     auto fn = morph_linear_kernel<NK_, NCT_, EV_, MK_>;                                                             \
     static bool attr_set[VMG_MAX_DEVICES] = {};                                                                     \
     const int dev = vmg_current_device();                                                                           \

@@ -23,6 +23,8 @@ CONV_GENERAL, CONV_KSPLIT, CONV_WS, CONV_LINEAR_WRES, CONV_WSTAT = 0, 2, 3, 4, 6
 # kernel families of vmg_conv_fwd_plan (include/vmg_hip.h VMG_CONV_FAM_*) and the length of its result
 CONV_FAM_IGEMM, CONV_FAM_KSPLIT, CONV_FAM_WS, CONV_FAM_LINEAR_WRES, CONV_FAM_WSTAT = 1, 2, 3, 4, 5
 CONV_PLAN_INTS = 11
+MORPHFC_PLAN_INTS = 8  # length of vmg_morphfc_plan's result (include/vmg_hip.h VMG_MORPHFC_PLAN_INTS)
+MORPH_ROUTE_ELEMENT, MORPH_ROUTE_LDS = 0, 1  # vmg_morph_tokens_route
 # weight-gradient kernels (vmg_conv_wgrad_last_kernel, include/vmg_hip.h VMG_WGRAD_*)
 WGRAD_V1, WGRAD_3, WGRAD_3B, WGRAD_L2, WGRAD_7 = 1, 2, 3, 4, 5
 
@@ -122,6 +124,8 @@ SIGNATURES = {
     "vmg_morphfc_fwd": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                 c_void_p]),
     "vmg_morphfc_token_rows": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "vmg_morphfc_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "vmg_morph_tokens_route": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "vmg_morph_token_rows": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "vmg_morph_tokens_gather": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vmg_morph_tokens_scatter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -610,10 +610,44 @@ def morph_fused_ok(x: torch.Tensor, chunk: int, Cp: int) -> bool:
     return x.dtype == torch.bfloat16 and chunk in (8, 16) and Cp in MORPH_FUSED_CP and x.shape[-1] % 8 == 0 and Cp % chunk == 0
 
 
+MorphfcPlan = collections.namedtuple("MorphfcPlan", "NK NCT EVEN MASK ngroups ntiles nwg lds_bytes")
+
+
+def morphfc_plan(axis: str, chunk: int, BT: int, H: int, W: int, C: int, Cp: int, has_mask: bool = False, ncu: int = 0) -> MorphfcPlan:
+    """What morphfc_forward launches for the geometry (vmg_morphfc_plan, the function the entry point dispatches through; nothing is enqueued):
+    the morph_linear_kernel<NK, NCT, EVEN, MASK> instance, groups, 16-token tiles, workgroups and LDS bytes.  ncu = 0: the current device's
+    compute units.  Raises HipError with the entry point's message for what the kernel does not serve."""
+    if ncu <= 0:
+        ncu = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    plan = (ctypes.c_int * hip.MORPHFC_PLAN_INTS)()
+    hip.check(hip.lib().vmg_morphfc_plan(0 if axis == "h" else 1, chunk, BT, H, W, C, Cp, 1 if has_mask else 0, ncu, plan), "vmg_morphfc_plan")
+    p = MorphfcPlan(*plan)
+    return p._replace(EVEN=bool(p.EVEN), MASK=bool(p.MASK))
+
+
+def morph_tokens_route(dtype: torch.dtype, chunk: int, C: int, ld: int, aligned: bool = True) -> int:
+    """The kernel morph_tokens_gather / _scatter run (vmg_morph_tokens_route, which both dispatch through): hip.MORPH_ROUTE_LDS or
+    hip.MORPH_ROUTE_ELEMENT.  aligned: both pointers are 16-byte aligned."""
+    r = hip.lib().vmg_morph_tokens_route(hip.dtype_code(dtype), chunk, C, ld, 1 if aligned else 0)
+    if r < 0:
+        hip.check(r, "vmg_morph_tokens_route")
+    return r
+
+
+def _given_out(out: torch.Tensor, like: torch.Tensor, shape, what: str) -> torch.Tensor:
+    """A caller-owned output: contiguous, of the stated shape, dtype and device of `like`."""
+    hip.require_cuda(out)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device or not out.is_contiguous():
+        raise HipError(f"{what}: contiguous {like.dtype} {tuple(shape)} on {like.device} expected, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    return out
+
+
 def morphfc_forward(x: torch.Tensor, axis: str, chunk: int, Cp: int, pw: PackedConv, bias: Optional[torch.Tensor], relu: bool, in_scale: float,
-                    out_scale: float, mask: Optional[torch.Tensor] = None, want_tokens: bool = False):
+                    out_scale: float, mask: Optional[torch.Tensor] = None, want_tokens: bool = False, out: Optional[torch.Tensor] = None,
+                    tok_out: Optional[torch.Tensor] = None):
     """x (B,T,H,W,C) contiguous bf16 -> the branch output in the same layout (vmg_morphfc_fwd); mask: the data-gradient form.  want_tokens:
-    also returns the token matrix (rows, Cp) the GEMM multiplied (the weight gradient's operand), else None."""
+    also returns the token matrix (rows, Cp) the GEMM multiplied (the weight gradient's operand), else None.  out / tok_out: caller-owned
+    results (contiguous, x's shape / (vmg_morphfc_token_rows, Cp)); tok_out implies want_tokens."""
     hip.require_cuda(x, bias, mask)
     B, T, H, W, C = x.shape
     if not x.is_contiguous() or (mask is not None and (not mask.is_contiguous() or mask.shape != x.shape or mask.dtype != x.dtype)):
@@ -622,23 +656,24 @@ def morphfc_forward(x: torch.Tensor, axis: str, chunk: int, Cp: int, pw: PackedC
         raise HipError("morphfc: the pack must be a (Cp, Cp) 1x1 pack with all output tiles in one block")
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != Cp or not bias.is_contiguous()):
         raise HipError("morphfc: bias must be contiguous fp32 of length Cp")
-    out = torch.empty_like(x)
+    out = torch.empty_like(x) if out is None else _given_out(out, x, x.shape, "morphfc: out")
     ax = 0 if axis == "h" else 1
     tok = None
-    if want_tokens:
+    if want_tokens or tok_out is not None:
         rows = hip.lib().vmg_morphfc_token_rows(ax, chunk, B * T, H, W)
         if rows <= 0:
             raise HipError("morphfc: bad token geometry")
-        tok = torch.empty((rows, Cp), dtype=x.dtype, device=x.device)
+        tok = torch.empty((rows, Cp), dtype=x.dtype, device=x.device) if tok_out is None else _given_out(tok_out, x, (rows, Cp), "morphfc: tok_out")
     hip.check(hip.lib().vmg_morphfc_fwd(ax, chunk, x.data_ptr(), mask.data_ptr() if mask is not None else None, pw.buf.data_ptr(),
                                         bias.data_ptr() if bias is not None else None, out.data_ptr(), tok.data_ptr() if tok is not None else None,
                                         B * T, H, W, C, Cp, pw.cout_tiles, 1 if relu else 0, in_scale, out_scale, hip.stream_ptr()), "vmg_morphfc_fwd")
     return out, tok
 
 
-def morph_tokens_gather(x: torch.Tensor, axis: str, chunk: int, Cp: int, ld: Optional[int] = None) -> torch.Tensor:
+def morph_tokens_gather(x: torch.Tensor, axis: str, chunk: int, Cp: int, ld: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x (B,T,H,W,C) contiguous -> the MorphFC token matrix (rows, ld) of the reference's pad + rearrange chain (vmg_morph_tokens_gather): row
-    (group, k), feature p*S + s = x[position p of the group, channel k*S + s], zeros for padding positions / channels and for features >= Cp."""
+    (group, k), feature p*S + s = x[position p of the group, channel k*S + s], zeros for padding positions / channels and for features >= Cp.
+    out: a caller-owned contiguous (rows, ld) result."""
     hip.require_cuda(x)
     B, T, H, W, C = x.shape
     if not x.is_contiguous():
@@ -646,21 +681,22 @@ def morph_tokens_gather(x: torch.Tensor, axis: str, chunk: int, Cp: int, ld: Opt
     ld = Cp if ld is None else ld
     ax = 0 if axis == "h" else 1
     rows = hip.lib().vmg_morph_token_rows(ax, chunk, B * T, H, W)
-    tok = torch.empty((rows, ld), dtype=x.dtype, device=x.device)
+    tok = torch.empty((rows, ld), dtype=x.dtype, device=x.device) if out is None else _given_out(out, x, (rows, ld), "morph_tokens_gather: out")
     hip.check(hip.lib().vmg_morph_tokens_gather(hip.dtype_code(x.dtype), ax, chunk, x.data_ptr(), tok.data_ptr(), B * T, H, W, C, Cp, ld, hip.stream_ptr()),
               "vmg_morph_tokens_gather")
     return tok
 
 
-def morph_tokens_scatter(tok: torch.Tensor, axis: str, chunk: int, Cp: int, shape) -> torch.Tensor:
-    """The inverse layout + crop: tok (rows, ld >= Cp), row stride ld -> (B,T,H,W,C) (vmg_morph_tokens_scatter)."""
+def morph_tokens_scatter(tok: torch.Tensor, axis: str, chunk: int, Cp: int, shape, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The inverse layout + crop: tok (rows, ld >= Cp), row stride ld -> (B,T,H,W,C) (vmg_morph_tokens_scatter).  out: a caller-owned
+    contiguous (B,T,H,W,C) result."""
     hip.require_cuda(tok)
     B, T, H, W, C = shape
     ax = 0 if axis == "h" else 1
     rows = hip.lib().vmg_morph_token_rows(ax, chunk, B * T, H, W)
     if tok.dim() != 2 or tok.shape[0] != rows or tok.shape[1] < Cp or tok.stride(1) != 1:
         raise HipError(f"morph_tokens_scatter: token matrix ({rows}, >= {Cp}) expected, got {tuple(tok.shape)}")
-    out = torch.empty((B, T, H, W, C), dtype=tok.dtype, device=tok.device)
+    out = torch.empty((B, T, H, W, C), dtype=tok.dtype, device=tok.device) if out is None else _given_out(out, tok, (B, T, H, W, C), "morph_tokens_scatter: out")
     hip.check(hip.lib().vmg_morph_tokens_scatter(hip.dtype_code(tok.dtype), ax, chunk, tok.data_ptr(), out.data_ptr(), B * T, H, W, C, Cp, tok.stride(0),
                                                  hip.stream_ptr()), "vmg_morph_tokens_scatter")
     return out
