@@ -451,6 +451,37 @@ int vmg_group_reduce2(int dtype, const void* a, const void* b0, const void* b1, 
 int vmg_mix2_fwd(int dtype, const void* h, const void* w, const float* coef, void* y, int64_t rows, int64_t R, int C, void* stream);
 int vmg_mix2_bwd(int dtype, const void* dy, const float* coef, const float* add, void* dh, void* dw, int64_t rows, int64_t R, int C, void* stream);
 
+/* ---- depthwise 3x3 convolution with optional ReLU6 on the source and on the output: the middle layer of the MBConv spatial mixer
+ * (mixer_type 'mbconv'; models/CNNs.py InvertedResidual :159-185, Multi_MBConv :187-201): csrc/dwconv.hip.
+ * e, a, da, de (N, H, W, C) channels-last, fp32 / bf16; w (C, 1, 3, 3) and b (C) fp32, read as stored; stride 1, zero padding 1; fp32 accumulation,
+ * one rounding at the store.  src_act, out_act: 0 none, 1 ReLU6, independently.  ReLU6' = 1 only where 0 < v < 6, strictly (torch's).
+ *   vmg_dwconv3_fwd          a = act_out( sum_{ky,kx} w[c,ky,kx] * act_src(e)[y+ky-1, x+kx-1, c] + b[c] );  out-of-image taps contribute 0
+ *   vmg_dwconv3_bwd_data     g = da * act_out'(a), formed on load;  de = act_src'(e) * sum_{ky,kx} w[c,ky,kx] * g[y-ky+1, x-kx+1, c].  One launch.
+ *                            act_out' is taken from the stored output a (no pre-activation is kept); a is read only with out_act and e only
+ *                            with src_act (either may be null otherwise).
+ *   vmg_dwconv3_bwd_weight   dW[c,ky,kx] = sum_{n,y,x} g * act_src(e)[y+ky-1, x+kx-1, c];  db[c] = sum_{n,y,x} g, fp32, written (accumulate 0) or
+ *                            added to dW / db (1).  Two launches: per-workgroup partial sums (lanes added through LDS in lane order) into the
+ *                            caller's workspace ws, then the partials added in index order.  No atomics; the grid is a function of the geometry
+ *                            alone, so the bits repeat from run to run.
+ *   vmg_dwconv3_wgrad_ws_bytes  bytes of ws for that geometry (partials * C * 10 floats); -1 where the plan refuses.
+ *   vmg_dwconv3_plan         a pure host function (no device query): plan[0] route -- VMG_DWCONV_VECTOR (16-byte vectors: C a multiple of 8 bf16 /
+ *                            4 fp32 and aligned16, every activation pointer on a 16-byte boundary, non-zero) or VMG_DWCONV_ELEMENT (any C, any
+ *                            element-aligned pointer); [1], [2] the pixel tile (rows, columns) of a workgroup; [3] its channel block; [4] the grid
+ *                            of the forward and the data gradient; [5] their LDS bytes; [6] the first-stage partial count of the weight gradient;
+ *                            [7] its first-stage grid.  The entries dispatch through it.  N * H * W * C >= 2^31 is REFUSED (non-zero return).
+ * Non-zero (vmg_last_error), without a launch, on a null pointer, N, H, W or C < 1, an unknown dtype or flag, a pointer not aligned to its
+ * element, a workspace that is too small. */
+#define VMG_DWCONV_VECTOR 1
+#define VMG_DWCONV_ELEMENT 2
+#define VMG_DWCONV_PLAN_INTS 8
+int vmg_dwconv3_plan(int dtype, int N, int H, int W, int C, int aligned16, int* plan);
+int vmg_dwconv3_fwd(int dtype, int src_act, int out_act, const void* e, const float* w, const float* b, void* a, int N, int H, int W, int C, void* stream);
+int vmg_dwconv3_bwd_data(int dtype, int src_act, int out_act, const void* da, const void* a, const void* e, const float* w, void* de, int N, int H, int W,
+                         int C, void* stream);
+int64_t vmg_dwconv3_wgrad_ws_bytes(int dtype, int N, int H, int W, int C);
+int vmg_dwconv3_bwd_weight(int dtype, int src_act, int out_act, const void* da, const void* a, const void* e, float* dW, float* db, int N, int H, int W,
+                           int C, int accumulate, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Flow-guided sampling of the trajectory recurrence (models/trajectory.py:71-116 flow_warp, :329-333, :414-417).
  * flow: (N,H,W,2) fp32 pixel offsets (x then y); coordinates follow flow_warp + F.grid_sample(align_corners=True).

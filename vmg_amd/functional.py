@@ -1278,6 +1278,45 @@ def patch_shift(x: torch.Tensor, inverse: bool = False, act: Optional[str] = Non
     return y.reshape(x.shape)
 
 
+class _DepthwiseConv3x3(_Fn):
+    """act(depthwise conv3x3(src_act(x)) + bias) on (N, H, W, C): one node, one launch forward, one for the data gradient, two ordered ones for
+    the parameters (csrc/dwconv.hip).  Saved: x, the output and the weight -- both ReLU6 derivatives come from those."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, src_act, act):
+        x = _ln_aligned(x.contiguous())
+        y = K.dwconv3_forward(x, weight, bias, src_act, act)
+        ctx.acts = (src_act, act)
+        ctx.save_for_backward(x, y, weight)
+        DEFERRED.claim(ctx, weight, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, weight = ctx.saved_tensors
+        src_act, act = ctx.acts
+        dy = _ln_aligned(dy.contiguous())
+        dx = K.dwconv3_backward_data(dy, y, x, weight, src_act, act) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.direct or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = K.dwconv3_backward_weight(dy, y, x, src_act, act, into=DEFERRED.into(ctx))
+        DEFERRED.done(ctx)
+        if ctx.direct:
+            return dx, None, None, None, None
+        return dx, dw, db, None, None
+
+
+def depthwise_conv3x3(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, src_act: Optional[str] = None, act: Optional[str] = None) -> torch.Tensor:
+    """act(conv3x3 depthwise(src_act(x)) + bias) of x (N, H, W, C) or (B, T, H, W, C), each frame on its own: stride 1, zero padding 1, weight
+    (C, 1, 3, 3) and bias (C,) fp32 as nn.Conv2d(C, C, 3, 1, 1, groups=C) stores them.  src_act, act: None or 'relu6'."""
+    if src_act not in (None, "relu6") or act not in (None, "relu6"):
+        raise ValueError(f"depthwise_conv3x3: src_act and act are None or 'relu6', got {src_act!r}, {act!r}")
+    if x.dim() not in (4, 5):
+        raise ValueError(f"depthwise_conv3x3: (B, T, H, W, C) or (N, H, W, C) expected, got {tuple(x.shape)}")
+    y = _DepthwiseConv3x3.apply(x.reshape(-1, *x.shape[-3:]), weight, bias, src_act, act)
+    return y.reshape(x.shape)
+
+
 class _TanhGate(_Fn):
     """(x + y) * tanh(y) (models/function.py:801-802)."""
 

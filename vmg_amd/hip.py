@@ -18,6 +18,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_GELU = 0, 1, 2, 3
 GATE_ACTS = {"tanh": 0, "sigmoid": 1, "relu": 2, "gelu": 3, "swish": 4}  # VMG_GATE_* of include/vmg_hip.h, by the symm_act names of the configs
 SHIFT_VECTOR, SHIFT_ELEMENT = 1, 2  # routes of the patch shift (vmg_patch_shift_plan, include/vmg_hip.h VMG_SHIFT_*)
+DWCONV_VECTOR, DWCONV_ELEMENT, DWCONV_PLAN_INTS = 1, 2, 8  # routes of the depthwise 3x3 (vmg_dwconv3_plan, include/vmg_hip.h VMG_DWCONV_*) and its result's length
 # conv kernel routes (ConvDesc.deep, include/vmg_hip.h VMG_CONV_*)
 CONV_GENERAL, CONV_KSPLIT, CONV_WS, CONV_LINEAR_WRES, CONV_WSTAT = 0, 2, 3, 4, 6
 # kernel families of vmg_conv_fwd_plan (include/vmg_hip.h VMG_CONV_FAM_*) and the length of its result
@@ -242,6 +243,12 @@ SIGNATURES = {
     "vmg_group_reduce2": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_void_p, c_int64, c_void_p]),
     "vmg_mix2_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
     "vmg_mix2_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p]),
+    "vmg_dwconv3_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "vmg_dwconv3_fwd": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "vmg_dwconv3_bwd_data": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "vmg_dwconv3_wgrad_ws_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "vmg_dwconv3_bwd_weight": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                       c_int64, c_void_p]),
     "vmg_prof_begin": (c_int, [c_void_p, c_int, c_int, c_int]),
     "vmg_prof_end": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int), POINTER(ctypes.c_double)]),
     "vmg_conv_wgrad": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int,

@@ -1616,6 +1616,95 @@ def se_mlp2_backward(dout: torch.Tensor, out: torch.Tensor, m: torch.Tensor, pre
     return dm.view(G, C), dw1.view(Hd, C), db1, dw2.view(Co, Hd), db2
 
 
+# ---- the depthwise 3x3 convolution of the MBConv mixer (csrc/dwconv.hip)
+DWCONV_ROUTES = {hip.DWCONV_VECTOR: "vector", hip.DWCONV_ELEMENT: "element"}
+DWCONV_ACTS = {None: 0, "relu6": 1}
+DwconvPlan = collections.namedtuple("DwconvPlan", "route tile_h tile_w chan_block grid lds_bytes partials wgrad_grid")
+
+
+def dwconv3_plan(N: int, H: int, W: int, C: int, dtype: torch.dtype, aligned: bool = True) -> DwconvPlan:
+    """What the depthwise 3x3 entries launch for the geometry (vmg_dwconv3_plan, the function they dispatch through; no device needed): route
+    ('vector' / 'element'), the workgroup's pixel tile and channel block, the grid and LDS bytes of the forward / data gradient, the
+    first-stage partial count and grid of the weight gradient.  aligned: every activation pointer is 16-byte aligned.  Raises HipError with
+    the entries' message for what they refuse (N * H * W * C >= 2^31)."""
+    plan = (ctypes.c_int * hip.DWCONV_PLAN_INTS)()
+    hip.check(hip.lib().vmg_dwconv3_plan(hip.dtype_code(dtype), int(N), int(H), int(W), int(C), int(bool(aligned)), plan), "vmg_dwconv3_plan")
+    p = DwconvPlan(*plan)
+    return p._replace(route=DWCONV_ROUTES[p.route])
+
+
+def dwconv3_route(C: int, dtype: torch.dtype, aligned: bool = True) -> str:
+    """The kernel a depthwise 3x3 of C channels runs on: 'vector' when C is a multiple of the 16-byte vector (8 bf16 / 4 fp32) and the
+    pointers are 16-byte aligned, else 'element' (from the plan; the route does not depend on N, H, W)."""
+    return dwconv3_plan(1, 1, 1, C, dtype, aligned).route
+
+
+def _dwconv_args(who, x, others, weight, bias, src_act, act):
+    hip.require_cuda(x, weight, bias, *others)
+    if x.dim() != 4 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous():
+        raise HipError(f"{who}: a contiguous fp32 / bf16 (N, H, W, C) tensor expected")
+    if any(t.shape != x.shape or t.dtype != x.dtype or not t.is_contiguous() for t in others):
+        raise HipError(f"{who}: contiguous operands of one shape / dtype expected")
+    if min(x.shape) < 1:
+        raise HipError(f"{who}: empty tensor")
+    C = x.shape[-1]
+    if weight.dtype != torch.float32 or not weight.is_contiguous() or tuple(weight.shape) != (C, 1, 3, 3):
+        raise HipError(f"{who}: a contiguous fp32 weight ({C}, 1, 3, 3) expected")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or tuple(bias.shape) != (C,)):
+        raise HipError(f"{who}: a contiguous fp32 bias ({C},) expected")
+    if src_act not in DWCONV_ACTS or act not in DWCONV_ACTS:
+        raise HipError(f"{who}: src_act and act are None or 'relu6', got {src_act!r}, {act!r}")
+    return DWCONV_ACTS[src_act], DWCONV_ACTS[act]
+
+
+def dwconv3_forward(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, src_act=None, act=None) -> torch.Tensor:
+    """act(depthwise conv3x3(src_act(x)) + bias) of x (N, H, W, C), stride 1, zero padding 1 (vmg_dwconv3_fwd)."""
+    sa, oa = _dwconv_args("dwconv3_forward", x, [], weight, bias, src_act, act)
+    N, H, W, C = x.shape
+    y = torch.empty_like(x)
+    hip.check(hip.lib().vmg_dwconv3_fwd(hip.dtype_code(x.dtype), sa, oa, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), N, H, W, C,
+                                        hip.stream_ptr()), "vmg_dwconv3_fwd")
+    return y
+
+
+def dwconv3_backward_data(dy: torch.Tensor, y: Optional[torch.Tensor], x: Optional[torch.Tensor], weight: torch.Tensor, src_act=None, act=None) -> torch.Tensor:
+    """The input gradient of dwconv3_forward in one launch (vmg_dwconv3_bwd_data): y, the stored output, is read with act; x with src_act."""
+    others = [t for t, on in ((y, act), (x, src_act)) if on is not None]
+    if any(t is None for t in others):
+        raise HipError("dwconv3_backward_data: y is needed with act, x with src_act")
+    sa, oa = _dwconv_args("dwconv3_backward_data", dy, others, weight, None, src_act, act)
+    N, H, W, C = dy.shape
+    dx = torch.empty_like(dy)
+    hip.check(hip.lib().vmg_dwconv3_bwd_data(hip.dtype_code(dy.dtype), sa, oa, dy.data_ptr(), y.data_ptr() if oa else None, x.data_ptr() if sa else None,
+                                             weight.data_ptr(), dx.data_ptr(), N, H, W, C, hip.stream_ptr()), "vmg_dwconv3_bwd_data")
+    return dx
+
+
+def dwconv3_backward_weight(dy: torch.Tensor, y: Optional[torch.Tensor], x: torch.Tensor, src_act=None, act=None, into=None):
+    """(dW (C, 1, 3, 3), db (C,)) fp32 of dwconv3_forward (vmg_dwconv3_bwd_weight: two ordered launches, no atomics, a workspace of
+    vmg_dwconv3_wgrad_ws_bytes).  into = (gW, gb): the sums are ADDED to these contiguous fp32 buffers (param.grad) and returned as such."""
+    if act is not None and y is None:
+        raise HipError("dwconv3_backward_weight: y is needed with act")
+    C = dy.shape[-1]
+    if into is not None:
+        dW, db = into
+        if any(t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda for t in into) or dW.numel() != 9 * C or db.numel() != C:
+            raise HipError("dwconv3_backward_weight: gradient buffers must be contiguous fp32 of the parameters' sizes")
+    else:
+        dW = torch.empty((C, 1, 3, 3), dtype=torch.float32, device=dy.device)
+        db = torch.empty(C, dtype=torch.float32, device=dy.device)
+    sa, oa = _dwconv_args("dwconv3_backward_weight", dy, [x] + ([y] if act is not None else []), dW.view(C, 1, 3, 3), db, src_act, act)
+    N, H, W, _ = dy.shape
+    code = hip.dtype_code(dy.dtype)
+    nbytes = int(hip.lib().vmg_dwconv3_wgrad_ws_bytes(code, N, H, W, C))
+    if nbytes < 0:
+        raise HipError(f"vmg_dwconv3_wgrad_ws_bytes: {hip.lib().vmg_last_error().decode()}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device)
+    hip.check(hip.lib().vmg_dwconv3_bwd_weight(code, sa, oa, dy.data_ptr(), y.data_ptr() if oa else None, x.data_ptr(), dW.data_ptr(), db.data_ptr(), N, H, W, C,
+                                               1 if into is not None else 0, ws.data_ptr(), nbytes, hip.stream_ptr()), "vmg_dwconv3_bwd_weight")
+    return dW, db
+
+
 class PackPlan:
     """One-launch repacking of many weights (vmg_pack_entry / vmg_pack_run): the entry array lives on the device and is rebuilt only
     when the set of packs (or a weight's / pack buffer's address) changes."""

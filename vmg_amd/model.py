@@ -280,6 +280,61 @@ class Mlp_cnn_shift(nn.Module):
         return lin(self.proj, FH.reweight_mix2(h, w, rw.fc1.weight, rw.fc1.bias, rw.fc2.weight, rw.fc2.bias))
 
 
+class InvertedResidual(nn.Module):
+    """The reference's inverted-residual block (models/CNNs.py:159-185): conv1x1 C -> 4C, ReLU6, depthwise conv3x3, ReLU6, conv1x1 4C -> C, + x.
+    The module tree is the reference's (bottleneck.{0,1,2}.0 are the nn.Conv2d parameter holders, ReLU6 children where it has them), so the
+    state-dict keys and their order are too.  The two 1x1 convolutions run on the Linear kernel without an activation; both ReLU6 ride on
+    the depthwise kernel (csrc/dwconv.hip), the second residual on the last Linear's epilogue."""
+
+    def __init__(self, in_channels=64, out_channels=None, expansion_factor=4, stride=1):
+        super().__init__()
+        if stride != 1:
+            raise NotImplementedError(f"InvertedResidual: stride 1 only (the reference's mixer never passes another), got {stride}")
+        self.stride = stride
+        out_channels = out_channels or in_channels
+        if out_channels != in_channels:
+            raise NotImplementedError("InvertedResidual: the residual needs out_channels == in_channels (the reference's forward does too)")
+        mid_channels = int(in_channels * expansion_factor)
+        self.bottleneck = nn.Sequential(
+            nn.Sequential(nn.Conv2d(in_channels, mid_channels, 1, 1), nn.ReLU6(inplace=True)),
+            nn.Sequential(nn.Conv2d(mid_channels, mid_channels, 3, stride, 1, groups=mid_channels), nn.ReLU6(inplace=True)),
+            nn.Sequential(nn.Conv2d(mid_channels, out_channels, 1, 1)))
+
+    def forward(self, x, x_res=None):
+        """x (B, T, H, W, C); x_res: a second autograd handle of x for the residual add (functional.layer_norm_fan / fan_out)."""
+        expand, dw, project = self.bottleneck[0][0], self.bottleneck[1][0], self.bottleneck[2][0]
+        e = FH.linear(x, expand.weight, expand.bias)
+        a = FH.depthwise_conv3x3(e, dw.weight, dw.bias, "relu6", "relu6")
+        return FH.linear(a, project.weight, project.bias, res=x if x_res is None else x_res)
+
+
+class Multi_MBConv(nn.Module):
+    """The MBConv spatial mixer (models/CNNs.py:187-201): num_blocks inverted-residual blocks under main.0, as make_layer nests them.  No
+    retention buffers, no state between calls."""
+
+    n_handles = 2  # consumers of the mixer's input: the first block's expansion and its residual
+
+    def __init__(self, embed_dim, expansion_factor=4, stride=1, num_blocks=10):
+        super().__init__()
+        self.main = nn.Sequential(nn.Sequential(*[InvertedResidual(in_channels=embed_dim, expansion_factor=expansion_factor, stride=stride)
+                                                  for _ in range(int(num_blocks))]))
+
+    def forward(self, x, residual=None):
+        """x: the normalised features (B,T,H,W,C), or a list of n_handles autograd handles of them (functional.layer_norm_fan).
+        residual = (res, drop_prob, training, scale): return res + DropPath(mixer(x)) * scale instead of mixer(x), as the MorphFC mixer does."""
+        xs = list(x) if isinstance(x, (list, tuple)) else [x] * self.n_handles
+        y = None
+        for i, blk in enumerate(self.main[0]):
+            h, r = (xs[0], xs[1]) if i == 0 else FH.fan_out(y, 2)
+            y = blk(h, r)
+        if y is None:  # (num_blocks = 0: the identity)
+            y = xs[0]
+        return y if residual is None else FH.residual_drop_path(residual[0], y, *residual[1:])
+
+
+MIXER_TYPES = ("mlps", "mbconv")  # models/function.py:1165-1193
+
+
 class sigmoid_symm(nn.Module):
     """sigmoid(x) - 0.5: the reference's symmetric sigmoid (models/function.py:18-27), parameter-free."""
 
@@ -395,11 +450,16 @@ class TAB(nn.Module):
     """x += DP(spatial(LN2(x))) * s; x += DP(ffn(LN3(x))) * s (models/function.py:1139-1217)."""
 
     def __init__(self, embed_dim, chunk_h, chunk_w, mlp_ratio, n_groups, qkv_bias, drop_path, ffn, mixer_scaling, channel_mixer, gating=True,
-                 symm=True, symm_act="tanh"):
+                 symm=True, symm_act="tanh", mixer_type="mlps", mixer_n=None):
         super().__init__()
         self.spatial_scale = mixer_scaling
         self.norm2 = nn.LayerNorm(embed_dim)
-        self.spatial_mixing = Enhanced_MorphFCs_decay(embed_dim, chunk_h, chunk_w, qkv_bias, channel_mixer, gating, symm, symm_act)
+        if mixer_type == "mlps":
+            self.spatial_mixing = Enhanced_MorphFCs_decay(embed_dim, chunk_h, chunk_w, qkv_bias, channel_mixer, gating, symm, symm_act)
+        elif mixer_type == "mbconv":
+            self.spatial_mixing = Multi_MBConv(embed_dim, expansion_factor=4, stride=1, num_blocks=mixer_n)
+        else:
+            raise NotImplementedError(f"mixer_type {mixer_type!r}: 'mlps' or 'mbconv'")
         self.norm3 = nn.LayerNorm(embed_dim)
         if ffn == "vanilla":
             self.channel_mixing = Mlp(embed_dim, int(embed_dim * mlp_ratio))
@@ -661,7 +721,8 @@ class Mlp_encoder(nn.Module):
 
     def __init__(self, embed_dim, depth, segm, chunk_dim_h, chunk_dim_w, mlp_ratio, n_groups, qkv_bias, drop_path, window_size,
                  n_nonkeyframes, aligned, empty_aligned, traj_r_n, traj_heads, if_smooth, region_range, ffn_type, r_scaling, twins,
-                 traj_scale, m_scaling, if_local_fuse, channel_mixer, traj_mode="wins", gating=True, symm=True, symm_act="tanh"):
+                 traj_scale, m_scaling, if_local_fuse, channel_mixer, traj_mode="wins", gating=True, symm=True, symm_act="tanh", mixer_type="mlps",
+                 mixer_n=None):
         super().__init__()
         self.aligned, self.empty = aligned, empty_aligned
         self.takes_flows, self.keeps_flow_scale = self.flow_use(aligned, empty_aligned)
@@ -672,7 +733,7 @@ class Mlp_encoder(nn.Module):
             self.local_cnn = nn.Conv2d(embed_dim, embed_dim, 3, 1, 1)
         self.mlp_blocks = nn.ModuleList([TAB(embed_dim, chunk_dim_h, chunk_dim_w, mlp_ratio, n_groups, qkv_bias,
                                              drop_path[i] if isinstance(drop_path, list) else drop_path, ffn_type, m_scaling,
-                                             channel_mixer, gating, symm, symm_act) for i in range(depth)])
+                                             channel_mixer, gating, symm, symm_act, mixer_type, mixer_n) for i in range(depth)])
         if aligned:
             raise NotImplementedError("temporal_type=True (DCN alignment) is not configured by any shipped config")
         if aligned is None:
@@ -746,9 +807,13 @@ class InputProj(nn.Module):
 
 
 class VMG(nn.Module):
-    def __init__(self, in_chans=3, embed_dim=[112, 224, 224, 448, 448, 224, 224, 112], depths=[8, 8, 8, 8, 8, 8, 8, 8],
-                 num_heads=[2, 4, 8, 16, 16, 8, 4, 2], num_frames=7,
-                 window_sizes=[(4, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 4)], mdsc=True, if_concat=False,
+    # The four stage lists default to SEVEN entries where the reference's have eight (models/vmg.py:177-181: embed_dim [112, 224, 224, 448, 448, 224, 224,
+    # 112] and so on).  n entries make n // 2 + 1 encoder and n // 2 decoder stages (:213-215, commented "# 7", "# 4", "# 3" there), so an even n asks
+    # for n + 1 stages and four scales serve seven: the reference's own VMG() raises IndexError (:290).  The duplicated bottleneck entry is dropped
+    # here, every other default is the reference's, and VMG() constructs.  A call that passes its stage lists, as every config does, is unaffected.
+    def __init__(self, in_chans=3, embed_dim=[112, 224, 224, 448, 224, 224, 112], depths=[8, 8, 8, 8, 8, 8, 8],
+                 num_heads=[2, 4, 8, 16, 8, 4, 2], num_frames=7,
+                 window_sizes=[(4, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 4), (4, 4)], mdsc=True, if_concat=False,
                  mlp_ratio=4., n_groups=1, qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1,
                  norm_layer=nn.LayerNorm, patch_norm=True, back_RBs=0, spynet_pretrained=None, image_size=[64, 112], is_train=True,
                  if_print=False, ltam=True, traj_win=[16, None, None, None], traj_keyframes_n=[3, None, None, None],
@@ -765,8 +830,11 @@ class VMG(nn.Module):
             raise NotImplementedError("VMG HIP path: ltam/retention_decay/non_linear/relu_scale must be true, "
                                       "relu_scale_norm/if_concat false (as in all shipped configs)")
         symm_act = symm_act_name(symm_act)  # ValueError for anything but the reference's five (models/vmg.py:265-274)
-        if traj_mode not in ("wins", "max") or any(m != "mlps" for m in mixer_type[:len(depths) // 2 + 1]):
-            raise NotImplementedError("VMG HIP path: traj_mode 'wins' or 'max', mixer_type='mlps' only")
+        if traj_mode not in ("wins", "max"):
+            raise NotImplementedError("VMG HIP path: traj_mode 'wins' or 'max'")
+        bad = [m for m in mixer_type if m not in MIXER_TYPES]
+        if bad:
+            raise NotImplementedError(f"mixer_type {bad[0]!r}: every entry is 'mlps' or 'mbconv' (the reference raises on any other string too)")
         if back_RBs != 0 or traj_refine is not None:
             raise NotImplementedError("back_RBs > 0 / traj_refine are not used by any shipped config")
         self.num_layers = len(depths)
@@ -798,16 +866,16 @@ class VMG(nn.Module):
             self.local_cnn = nn.Conv2d(embed_dim[0], embed_dim[0], 3, 1, 1)
         self.input_proj = InputProj(in_chans, embed_dim[0])
 
-        def stage(dim, depth, heads, ch, cw, dpr, ws, nk, al, rn, th):
+        def stage(dim, depth, heads, ch, cw, dpr, ws, nk, al, rn, th, mt, mn):
             return Mlp_encoder(dim, depth, heads, ch, cw, mlp_ratio, n_groups, qkv_bias, dpr, ws, nk, al, temporal_empty, rn, th,
                                flow_smooth, smooth_region_range, ffn_type, r_scaling, twins, traj_scale, m_scaling, if_local_fuse,
-                               channel_mixer, traj_mode, gating, symm, symm_act)
+                               channel_mixer, traj_mode, gating, symm, symm_act, mt, mn)
 
         self.encoder_layers, self.upsample, self.downsample = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
         for i in range(self.num_enc_layers):
             self.encoder_layers.append(stage(embed_dim[i], depths[i], num_heads[i], self.chunk_h[i], self.chunk_w[i],
                                              enc_dpr[sum(depths[:i]):sum(depths[:i + 1])], window_sizes[i], traj_keyframes_n[i],
-                                             temporal_type[i], traj_res_n[i], traj_heads[i]))
+                                             temporal_type[i], traj_res_n[i], traj_heads[i], mixer_type[i], mixer_n[i]))
             if i != self.num_enc_layers - 1:
                 self.downsample.append(UpdownkeepSampling(embed_dim[i], embed_dim[i + 1], "down"))
             else:
@@ -818,7 +886,7 @@ class VMG(nn.Module):
             self.decoder_layers.append(stage(embed_dim[i + ne], depths[i + ne], num_heads[i + ne], self.chunk_h[-i - 2],
                                              self.chunk_w[-i - 2], dec_dpr[sum(dec_depths[:i]):sum(dec_depths[:i + 1])],
                                              window_sizes[i + ne], traj_keyframes_n[-i - 2], temporal_type[-i - 2], traj_res_n[i + ne],
-                                             traj_heads[-i - 2]))
+                                             traj_heads[-i - 2], mixer_type[-i - 2], mixer_n[-i - 2]))
             if i != self.num_dec_layers - 1:
                 self.upsample.append(UpdownkeepSampling(embed_dim[i + ne], embed_dim[i + ne + 1], "up"))
 
