@@ -307,8 +307,11 @@ int vmg_conv_wgrad_plan(int entry, int dtype, int ks, int nprob, int npairs, int
  * vmg_pixel_unshuffle_actgrad  the backward of "conv -> PixelShuffle(2) -> activation" in front of the conv's gradients, one pass:
  *                    out[n,y,x,4c+2i+j] = dy[n,2y+i,2x+j,c] * alpha * act'(ref[n,2y+i,2x+j,c]); dy / ref (N,2H,2W,c), out (N,H,W,4c);
  *                    ref = null with VMG_ACT_NONE.  c a multiple of the 16-byte vector (8 bf16 / 4 fp32).  models/vmg.py:629-630.
- * vmg_frame_gather   dst frame f = sum_{k < nsrc} src frame idx[f*nsrc + k] (nsrc 1 or 2; idx: device int32, < 0 = no term; fp32 sum, one
- *                    rounding); frames = contiguous blocks of frame_elems elements (whole 16-byte vectors).  The two direction sweeps of
+ * vmg_frame_gather   dst frame f = sum_{k < nsrc} src frame idx[f*nsrc + k] (nsrc 1 or 2; idx: device int32; fp32 sum, one rounding);
+ *                    frames = contiguous blocks of frame_elems elements (whole 16-byte vectors).  nsrc = 2: an index < 0 = no term (both
+ *                    < 0: a frame of +0).  nsrc = 1 is a plain copy and has no such case: every index must be >= 0.  The table is device
+ *                    data, so NOTHING checks it (that would cost a synchronisation): 0 <= idx < n_src_frames (nsrc = 1), idx < n_src_frames
+ *                    (nsrc = 2) is the CALLER's responsibility; an index outside reads out of bounds.  The two direction sweeps of
  *                    the recurrence (models/trajectory.py:323-392, 407-477) run as one batch: step j works on [frame t-1-j | frame j] of
  *                    every clip -- that arrangement of the (n, t) features is one gather, its gradient one gather-add.
  * vmg_sum_n          out = the sum of 2..4 tensors of one dtype (fp32 sum, one rounding): the gradient of a tensor with several consumers -- the hidden

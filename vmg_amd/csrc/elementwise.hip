@@ -502,7 +502,9 @@ __global__ __launch_bounds__(256) void frame_gather_kernel(const T* __restrict__
   Vec* d = reinterpret_cast<Vec*>(dst) + (long long)f * fv;
   for (long long v = v0 + threadIdx.x; v < v1; v += 256) {
     if (NSRC == 1) {
-      d[v] = reinterpret_cast<const Vec*>(src)[(long long)s[0] * fv + v];  // (the host rejects a negative index when nsrc = 1)
+      // (no "no term" here: with nsrc = 1 every index must be >= 0 -- the CALLER's contract, like idx < n_src_frames.  Nothing on the host
+      //  checks it: the table is device data, and reading it back would cost a synchronisation)
+      d[v] = reinterpret_cast<const Vec*>(src)[(long long)s[0] * fv + v];
     } else {
       float acc[VN];
 #pragma unroll

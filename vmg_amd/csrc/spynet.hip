@@ -23,8 +23,14 @@ __global__ void avgpool2_kernel(const T* __restrict__ x, T* __restrict__ y, int 
   }
 }
 
-// torch's bilinear source index for align_corners=True: src = dst * (in - 1) / (out - 1)
+// torch's bilinear source index for align_corners=True: src = dst * (in - 1) / (out - 1), as torch computes it for a float tensor: the product
+// is ROUNDED to fp32, and index and weight both come from that one number.  Without the pragma the compiler contracts `s - (float)i0` into
+// fma(ratio, dst, -i0): the weight then came from the unrounded product and the index from the rounded one -- off from torch's weight by up to
+// half an ulp of s (2^-24 s: 3e-5 at column 1000, found by tests/test_glue_kernels_gpu.py at 64 x 112), and below 0 wherever the product
+// rounds up to an integer.  The pragma holds under the compiler's default -ffp-contract=fast-honor-pragmas; a build with plain
+// -ffp-contract=fast would ignore it and bring the fma back -- the forward's 8 x 2^-24 S bound in that test is what would notice.
 __device__ __forceinline__ void ac_src(int dst, float ratio, int in, int& i0, int& i1, float& l1) {
+#pragma clang fp contract(off)
   const float s = ratio * (float)dst;
   i0 = (int)s;
   if (i0 > in - 1) i0 = in - 1;

@@ -391,8 +391,10 @@ def pixel_shuffle(x: torch.Tensor, N: int, H: int, W: int) -> torch.Tensor:
 
 def frame_gather(src: torch.Tensor, idx: torch.Tensor, n_dst: int, frame_shape) -> torch.Tensor:
     """dst frame f = sum_k src frame idx[f, k] (vmg_frame_gather): src contiguous, its leading dims flattened into frames of prod(frame_shape)
-    elements; idx (n_dst, 1 or 2) int32 on the device, every entry < number of source frames (the CALLER's contract: the table is device data),
-    < 0 = no term.  Returns (n_dst, *frame_shape)."""
+    elements; idx (n_dst, 1 or 2) int32 on the device.  Two columns: an entry < 0 = no term (both < 0: a frame of +0).  One column: a plain
+    copy, every entry must be >= 0.  Every entry < number of source frames.  The table is device data, so neither bound is checked here or in
+    vmg_frame_gather (it would cost a synchronisation): both are the CALLER's responsibility, and an entry outside them reads out of bounds.
+    Returns (n_dst, *frame_shape)."""
     hip.require_cuda(src, idx)
     fe = 1
     for d in frame_shape:
