@@ -837,7 +837,10 @@ int vmg_resblock_chain_fwd_q8(const vmg_chainq8_desc* c, void* stream);
 /* ---- clip_grad_norm_ over a flat fp32 gradient buffer (reference: torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2) as
  * called in tools/Trainer.py:141-143, 166-167 when train.if_grad_clip is set) -------------------------------------------------
  * g: n floats, 16-byte aligned; workspace: vmg_grad_clip_ws_bytes() bytes of device memory; norm_out (DEVICE, 2 floats): the total
- * L2 norm and the applied coefficient min(1, max_norm / (norm + 1e-6)).  Two launches, fixed summation order (bit-reproducible). */
+ * L2 norm and the applied coefficient clamp(max_norm / (norm + 1e-6), max = 1) in float arithmetic.  As in torch, a NaN gradient makes
+ * the norm, the coefficient and every gradient NaN, an Inf makes the coefficient 0 (finite gradients become +-0, the Inf NaN); a
+ * coefficient of 1 leaves the buffer untouched.  Two launches, fixed summation order (bit-reproducible).  After a call the workspace
+ * holds 1024 doubles: block b's sum of squares over its ceil((n / 4) / 1024) float4, the n % 4 tail in the last block's. */
 int64_t vmg_grad_clip_ws_bytes(void);
 int vmg_grad_clip_norm(float* g, int64_t n, float max_norm, void* workspace, float* norm_out, void* stream);
 

@@ -43,7 +43,10 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
 // ---- clip_grad_norm_ over the flat gradient buffer (tools/Trainer.py:141-143, 166-167: torch.nn.utils.clip_grad_norm_, norm_type 2) ----
 // Two launches, no atomics: per-block sums of squares over fixed contiguous chunks (fixed order inside a block: a strided walk, wave
 // shuffles, the four waves through LDS), then every block of the second launch adds the partials in index order -- in double -- and
-// scales its own chunk by min(1, max_norm / (norm + 1e-6)).  The result is the same bits on every run and for any gradient-arrival order.
+// scales its own chunk by clamp(max_norm / (norm + 1e-6), max=1); a coefficient of 1 leaves the buffer untouched.  As in torch, a NaN among
+// the gradients makes the norm and the coefficient NaN and with them every gradient (a diverged run must not train on), and an Inf makes
+// the coefficient 0: finite gradients become +-0, the Inf becomes NaN.  The result is the same bits on every run and for any
+// gradient-arrival order.
 constexpr int CLIP_BLOCKS = 1024;
 
 __device__ __forceinline__ double block_sum_double(double v, double* sm) {
@@ -84,9 +87,9 @@ __global__ __launch_bounds__(256) void grad_clip_scale_kernel(float* __restrict_
   const double total = block_sum_double(t, sm);
   const float norm = (float)sqrt(total);
   float coef = max_norm / (norm + 1e-6f);
-  coef = coef < 1.0f ? coef : 1.0f;
+  coef = coef > 1.0f ? 1.0f : coef;  // (a NaN coefficient stays NaN)
   if (blockIdx.x == 0 && threadIdx.x == 0) { norm_out[0] = norm; norm_out[1] = coef; }
-  if (coef >= 1.0f) return;
+  if (coef >= 1.0f) return;  // (false for NaN: the scaling pass runs)
   const long long n4 = n >> 2;
   const long long per = (n4 + CLIP_BLOCKS - 1) / CLIP_BLOCKS;
   const long long lo = blockIdx.x * per, hi = (lo + per < n4) ? lo + per : n4;
